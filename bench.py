@@ -2,12 +2,18 @@
 256x256 face-VAE step; MFMA utilisation).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--res 256] [--dtype bf16]
+                    [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
 
 One step = zero_grad -> forward (AFE trunk, reparam, Generator trunk) -> MSE + KL ->
 backward (+ RCCL gradient all-reduce, SyncBN collectives when N > 1) -> Adam, on synthetic
 VoxCeleb-shaped frames x ~ U[0,1) [B,3,H,H] and eps ~ N(0,1), resident in HBM before the
 timed region.  Weak scaling: B images per GPU.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds what takes
+runs of its own: the dominant kernel's HIP-event timing (`roofline`), the CPU oracle's rate
+(`cpu_baseline`) and the first step's `parity` against it.  --dump-outputs DIR writes what the
+last timed step computed as DIR/<name>.npy (float32; the same arguments give the same inputs).
 """
 import argparse
 import json
@@ -18,6 +24,7 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
@@ -41,7 +48,13 @@ def parse():
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32", "fp8"],
                     help="fp8: the 3x3 128-multiple-channel convs' fwd + dgrad on e4m3 (config C5)")
     ap.add_argument("--no-syncbn", action="store_true", help="per-rank BN statistics (labelled)")
-    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="CPU-baseline budget (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also time the dominant kernel with HIP events (roofline), run the CPU baseline and "
+                         "report the first step's parity against it; a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32, <= 64 MB in all)")
+    ap.add_argument("--cpu-seconds", type=float, default=20.0,
+                    help="CPU-baseline budget of a --full run (0 = skip)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = every core this process may use")
     ap.add_argument("--graph", type=int, default=1,
                     help="1 (default): replay the captured step (StepGraph: one HIP graph at one process, "
@@ -146,6 +159,26 @@ def pmc_counters(cfg, B, dtype, fam, avg_ms):
     return out
 
 
+DUMP_SAMPLE_SEED = 4321
+# largest number of elements written per array (float32): 8M + 2 x 2M + 1M + scalars < 64 MB
+DUMP_CAPS = {"y": 8 << 20, "mu": 2 << 20, "logstd": 2 << 20, "params": 1 << 20}
+
+
+def dump_outputs(path, tensors):
+    """Write each tensor of `tensors` (name -> device tensor) as path/<name>.npy in float32.  An
+    array above its DUMP_CAPS entry is written as a fixed sample: the elements of the flattened
+    array at sorted indices drawn from a seeded generator, the same for every run of the same
+    shapes."""
+    os.makedirs(path, exist_ok=True)
+    for name, t in tensors.items():
+        t = t.detach().float().reshape(-1)
+        cap = DUMP_CAPS.get(name)
+        if cap is not None and t.numel() > cap:
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).integers(0, t.numel(), size=cap))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy().astype(np.float32))
+
+
 def main():
     args = parse()
 
@@ -178,6 +211,9 @@ def main():
     # multiplies in the backward); the weighted sum is formed only for the returned value
     w_seed = (torch.tensor(cfg.w_R, device="cuda"), torch.tensor(cfg.w_K, device="cuda"))
 
+    dump = args.dump_outputs if rank == 0 else None
+    held = {}      # --dump-outputs: the last step's image and latent moments (a captured step's static outputs)
+
     def step(keep=None):
         opt.zero_grad(set_to_none=True)
         y, mu, logstd = net(x, eps)
@@ -186,6 +222,8 @@ def main():
         opt.step()
         if keep is not None:
             keep.extend([y.detach(), R.detach(), K.detach()])
+        if dump:
+            held.update(y=y.detach(), mu=mu.detach(), logstd=logstd.detach())
         return R.detach(), K.detach()
 
     # dominant kernel family: the ResBlock 3x3 256->256 convs at the latent resolution
@@ -199,11 +237,15 @@ def main():
 
     use_graph = bool(args.graph)
     run = step
-    # warm-up step 1 (from the initial weights): its image and losses are the GPU side of the
-    # parity record (compared with the CPU oracle's first step in cpu_baseline)
-    first = []
-    step(first)
-    gpu_first = (first[0].float().cpu(), first[1].item(), first[2].item())
+    # warm-up step 1 (from the initial weights): with --full its image and losses are the GPU
+    # side of the parity record (compared with the CPU oracle's first step in cpu_baseline)
+    gpu_first = None
+    if args.full:
+        first = []
+        step(first)
+        gpu_first = (first[0].float().cpu(), first[1].item(), first[2].item())
+    else:
+        step()
     if use_graph:
         # W - 1 more eager warm-up steps, then one step captured into a HIP graph; two untimed replays
         sg = fv.StepGraph(step, [opt], warmup=max(1, args.warmup - 1)).capture()
@@ -216,7 +258,7 @@ def main():
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
-    timer.enabled = not use_graph
+    timer.enabled = args.full and not use_graph
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -227,7 +269,13 @@ def main():
         dist.barrier()
     t = time.perf_counter() - t0
     timer.enabled = False
-    if use_graph:
+    if dump:
+        # what the last timed step returned (R, K) and computed: the image, the latent moments
+        # and the weights after its Adam update (sampled where an array is large)
+        params = torch.cat([p.detach().float().reshape(-1) for p in model.parameters()])
+        dump_outputs(dump, {"R": loss[0], "K": loss[1], "params": params, **held})
+        del params
+    if args.full and use_graph:
         # the roofline kernel's launch durations: HIP events around its launches over K eager
         # steps right after the graph-timed region (ROCm refuses event nodes inside a capture)
         timer.enabled = True
@@ -302,7 +350,7 @@ def main():
         "cpu_baseline": None,
         "parity": None,
     }
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0:
         out["cpu_baseline"], out["parity"] = cpu_baseline(args, cfg, B, gpu_first)
     if rank == 0:
         print(json.dumps(out), flush=True)

@@ -17,7 +17,8 @@ KLDivergenceLoss / ReconLoss are instantiated (nothing of torchvision is touched
 
 Fixtures written next to this script:
   toy_step.pt    toy config (64², B=4): init state, x, eps, step-1 outputs/grads/state,
-                 step-3 losses/state.
+                 step-3 losses/state.  (toy_step.pt and blocks.pt are written in parts,
+                 *.partN.pt, each below 1 MiB: tests/golden_io.py.)
   blocks.pt      per-block cases (ConvBlock2D CNA/NAC/leaky, DownBlock2D, UpBlock2D,
                  ResBlock2D; fwd output, input grad, param grads, updated buffers).
   full256.pt     full config (256², B=2): per-key checksums of the seed-0 init, losses of
@@ -31,6 +32,8 @@ import torch
 
 REF = "/root/reference"
 HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(HERE))
+from golden_io import save_golden  # noqa: E402  (fixtures above 1 MiB are written in parts)
 
 
 def import_reference():
@@ -110,7 +113,7 @@ def make_toy(models, losses):
                           loss=h1["loss"], grads=h1["grads"], state=h1["state"]),
                step3=dict(R=torch.stack([h["R"] for h in hist]), K=torch.stack([h["K"] for h in hist]),
                           y=h3["y"], state=h3["state"]))
-    torch.save(out, os.path.join(HERE, "toy_step.pt"))
+    save_golden(out, "toy_step.pt")
 
 
 def make_full(models, losses):
@@ -153,7 +156,7 @@ def make_blocks(modules):
     run("up_sn", lambda: modules.UpBlock2D(32, 16, True), (2, 32, 8, 8), 14)
     run("res_sn", lambda: modules.ResBlock2D(32, True), (2, 32, 8, 8), 15)
     run("same", lambda: modules.SameBlock2D(32, 64, False), (2, 32, 8, 8), 16)
-    torch.save(cases, os.path.join(HERE, "blocks.pt"))
+    save_golden(cases, "blocks.pt")
 
 
 def main():

@@ -8,6 +8,8 @@ import subprocess
 import pytest
 import torch
 
+from golden_io import load_golden
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HDR = os.path.join(ROOT, "include", "facevae.h")
 LIB = os.path.join(ROOT, "face-vae_amd", "libfacevae.so")
@@ -83,7 +85,7 @@ def test_bn_record_geometry_covers_every_pixel(lib_built, shape):
 def test_state_dict_and_init_match_reference():
     import fvamd  # noqa: F401
     import facevae_amd as fv
-    g = torch.load(os.path.join(ROOT, "tests", "golden", "toy_step.pt"), weights_only=True)
+    g = load_golden("toy_step.pt")
     torch.manual_seed(0)
     m = fv.FaceVAE(fv.FaceVAEConfig.toy())
     sd = m.state_dict()

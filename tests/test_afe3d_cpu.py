@@ -8,13 +8,14 @@ import torch
 
 import fvamd  # noqa: F401
 import facevae_amd as fv
+from golden_io import load_golden
 from oracle import facevae_cpu as O
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 
 
 def load():
-    return torch.load(os.path.join(GOLD, "afe3d.pt"), weights_only=True)
+    return load_golden("afe3d.pt")
 
 
 def rel(a, b):

@@ -20,6 +20,7 @@ import fvamd  # noqa: E402,F401
 import facevae_amd as fv  # noqa: E402
 from facevae_amd import _lib as L, ops3d  # noqa: E402
 from oracle import facevae_cpu as O  # noqa: E402  (checker only)
+from golden_io import load_golden  # noqa: E402
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 CL3 = torch.channels_last_3d
@@ -119,7 +120,7 @@ def test_depth_split_round_trip(shape):
 
 
 def _res3d_case(mode):
-    gd = torch.load(os.path.join(GOLD, "afe3d.pt"), weights_only=True)["res3d"]
+    gd = load_golden("afe3d.pt")["res3d"]
     torch.manual_seed(int(gd["seed"]))
     blk = fv.ResBlock3D(32, False).cuda().train().set_compute_dtype(mode)
     x = gd["x"].cuda().requires_grad_(True)
@@ -159,7 +160,7 @@ def test_resblock3d_bf16_vs_reference():
 
 
 def test_afe3d_fp32_matches_reference():
-    gd = torch.load(os.path.join(GOLD, "afe3d.pt"), weights_only=True)["afe3d"]
+    gd = load_golden("afe3d.pt")["afe3d"]
     torch.manual_seed(int(gd["seed"]))
     afe = fv.AFE(False, [16, 32], n_res=1, C=32, D=2).cuda().train().set_compute_dtype(torch.float32)
     y = afe(gd["x"].cuda())

@@ -16,6 +16,7 @@ pytestmark = pytest.mark.gpu
 import fvamd  # noqa: E402,F401
 import facevae_amd as fv  # noqa: E402
 from facevae_amd import ops  # noqa: E402
+from golden_io import load_golden  # noqa: E402
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 
@@ -52,7 +53,7 @@ def _step_fn(m, opt, x, eps, cfg):
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 def test_graph_replay_matches_eager(dtype):
-    g = torch.load(os.path.join(GOLD, "toy_step.pt"), weights_only=True)
+    g = load_golden("toy_step.pt")
     x, eps = g["x"].cuda(), g["eps"].cuda()
     cfg, ma, oa = _setup(dtype, g["init"])
     sa = _step_fn(ma, oa, x, eps, cfg)
@@ -127,7 +128,7 @@ def test_trainer_graph_mode_matches_eager():
     the Adam step counts equal the eager trainer's (the eager step in between must see the
     device step counter the replays advanced, and re-prepare the weights the graph shape had
     prepared)."""
-    g = torch.load(os.path.join(GOLD, "toy_step.pt"), weights_only=True)
+    g = load_golden("toy_step.pt")
     cfg = fv.FaceVAEConfig.toy()
     sizes = [2, 2, 1, 2, 2]
     trs = []
@@ -163,7 +164,7 @@ def test_trainer_loss_weights_seed_backward(graph):
     (w_R R + w_K K).backward() step on the same model -- bit-identical eager, within the
     graph-vs-eager Adam bar when graph-replayed."""
     import dataclasses
-    g = torch.load(os.path.join(GOLD, "toy_step.pt"), weights_only=True)
+    g = load_golden("toy_step.pt")
     cfg = dataclasses.replace(fv.FaceVAEConfig.toy(), w_R=10.0, w_K=0.2)
     torch.manual_seed(0)
     tr = fv.FaceVAETrainer(None, None, [], cfg.lr, cfg=cfg, compute_dtype=torch.float32, graph=graph)
@@ -199,7 +200,7 @@ def test_trainer_loss_weights_seed_backward(graph):
 def test_sn_bwd_batch_bit_identical(monkeypatch):
     """Spectral-norm backward terms batched at the end of backward (ops._SN_BATCH) against the
     per-conv launches: the same partial sums in the same order, bit-identical parameters."""
-    g = torch.load(os.path.join(GOLD, "toy_step.pt"), weights_only=True)
+    g = load_golden("toy_step.pt")
     x, eps = g["x"].cuda(), g["eps"].cuda()
     out = []
     for batch in (False, True):

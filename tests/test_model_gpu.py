@@ -16,12 +16,13 @@ pytestmark = pytest.mark.gpu
 import fvamd  # noqa: E402,F401
 import facevae_amd as fv  # noqa: E402
 from oracle import facevae_cpu as O  # noqa: E402  (checker only)
+from golden_io import load_golden  # noqa: E402
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 
 
 def load(name):
-    return torch.load(os.path.join(GOLD, name), weights_only=True)
+    return load_golden(name)
 
 
 def rel(a, b):

@@ -9,13 +9,14 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from golden_io import load_golden
 from oracle import facevae_cpu as O
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 
 
 def load(name):
-    return torch.load(os.path.join(GOLD, name), weights_only=True)
+    return load_golden(name)
 
 
 def rel(a, b):

@@ -4,7 +4,7 @@
 #
 #   smoke           __graft_entry__.smoke()
 #   test            pytest ${TESTS:-tests -m gpu} ${TESTK:+-k $TESTK}          -> gpurun_out/pytest.log
-#   bench           bench.py --steps 20 --warmup 5 $BENCH_ARGS                  -> gpurun_out/bench.log
+#   bench           bench.py --full --steps 20 --warmup 5 $BENCH_ARGS           -> bench.log in the output folder
 #   ab              alternating bench runs of $VARIANTS (";"-separated "ENV=.. -- bench args"
 #                   strings), $REPS rounds                                       -> gpurun_out/ab.log
 #   prof            rocprofv3 --kernel-trace --stats of bench.py $BENCH_ARGS     -> gpurun_out/prof_$TAG
@@ -41,7 +41,7 @@ step_test() {
 }
 
 step_bench() {
-  timeout -k 10 300 python bench.py --steps 20 --warmup 5 ${BENCH_ARGS:-} > $O/bench.log 2>&1 \
+  timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 ${BENCH_ARGS:-} > $O/bench.log 2>&1 \
     || { tail -20 $O/bench.log; return 1; }
   line $O/bench.log
 }
@@ -63,13 +63,13 @@ step_ab() {
 
 step_prof() {
   (cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$TAG -o run -- \
-    python3 $R/bench.py --steps 5 --warmup 2 --cpu-seconds 0 ${BENCH_ARGS:-} > $O/prof_$TAG.log 2>&1) \
+    python3 $R/bench.py --full --steps 5 --warmup 2 --cpu-seconds 0 ${BENCH_ARGS:-} > $O/prof_$TAG.log 2>&1) \
     || { tail -20 $O/prof_$TAG.log; return 1; }
   tail -1 $O/prof_$TAG.log | cut -c1-200
 }
 
 step_pmc() {
-  local B="$R/bench.py --steps 2 --warmup 1 --cpu-seconds 0 ${BENCH_ARGS:-}"
+  local B="$R/bench.py --full --steps 2 --warmup 1 --cpu-seconds 0 ${BENCH_ARGS:-}"
   (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/pmc_trace -o run -- \
     python3 $B > $O/pmc_trace.log 2>&1) || { echo "trace failed"; tail -5 $O/pmc_trace.log; return 1; }
   local i=0 c
@@ -128,7 +128,7 @@ step_c3pmc() {   # SQ + HBM counter passes over tools/conv3dbench.py ($C3_ARGS)
 step_configs() {
   local a
   for a in "--res 512 --batch 8" "--batch 64" "--batch 64 --dtype fp8"; do
-    timeout -k 10 300 python bench.py --steps 10 --warmup 3 --cpu-seconds 0 $a > $O/bench_cfg.log 2>&1 \
+    timeout -k 10 300 python bench.py --full --steps 10 --warmup 3 --cpu-seconds 0 $a > $O/bench_cfg.log 2>&1 \
       || { tail -20 $O/bench_cfg.log; return 1; }
     echo "[$a]"; line $O/bench_cfg.log
     cp $O/bench_cfg.log "$O/bench_$(echo $a | tr -d ' -').log"

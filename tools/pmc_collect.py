@@ -132,7 +132,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--trace", required=True)
     ap.add_argument("--pass", dest="passes", action="append", required=True)
-    ap.add_argument("--label", default="bench.py --steps 2 --warmup 1 --cpu-seconds 0")
+    ap.add_argument("--label", default="bench.py --full --steps 2 --warmup 1 --cpu-seconds 0")
     a = ap.parse_args()
     cnt = counters(a.passes)
     dur = durations(a.trace)
