@@ -9,8 +9,8 @@ through the C-ABI in include/facevae.h.
 """
 from . import _lib
 from .config import FaceVAEConfig, compute_dtype, set_compute_dtype
-from .losses import KLDivergenceLoss, L1Loss, PerceptualLoss, ReconLoss
-from .models import AFE, FaceVAE, Generator
+from .losses import FeatureMatchingLoss, GANLoss, KLDivergenceLoss, L1Loss, PerceptualLoss, ReconLoss
+from .models import AFE, Discriminator, FaceVAE, Generator
 from .modules import (Conv2d, ConvBlock2D, ConvBlock3D, ConvTranspose2dELR, DownBlock2D, ResBlock2D, ResBlock3D,
                       SameBlock2D, UpBlock2D)
 from .optim import Adam
@@ -19,7 +19,7 @@ from .graph import StepGraph
 
 __all__ = ["FaceVAEConfig", "compute_dtype", "set_compute_dtype", "KLDivergenceLoss", "L1Loss", "PerceptualLoss", "ReconLoss",
            "AFE", "FaceVAE", "Generator", "Conv2d", "ConvBlock2D", "ConvTranspose2dELR", "DownBlock2D", "ResBlock2D", "ResBlock3D", "ConvBlock3D", "SameBlock2D",
-           "UpBlock2D", "Adam", "distributed", "ops", "FaceVAETrainer"]
+           "UpBlock2D", "Adam", "distributed", "ops", "FaceVAETrainer", "Discriminator", "GANLoss", "FeatureMatchingLoss"]
 
 
 def __getattr__(name):

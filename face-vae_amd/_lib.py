@@ -207,6 +207,21 @@ _SIGS = {
     "fv_comm_async_error": (c_int, [c_void_p, POINTER(c_int)]),
     "fv_comm_count": (c_int, [c_void_p, POINTER(c_int)]),
     "fv_comm_abort": (c_int, [c_void_p]),
+    "fv_conv2d_s2_wk_elems": (c_size_t, [D]),
+    "fv_conv2d_s2_wt_elems": (c_size_t, [D]),
+    "fv_conv2d_s2_weight_prep": (c_int, [D, P, P, P, P, P]),
+    "fv_conv2d_s2_fwd": (c_int, [D, c_int, c_int, P, P, P, P, P]),
+    "fv_conv2d_s2_bwd_data": (c_int, [D, c_int, c_int, P, c_int, P, P, P]),
+    "fv_conv2d_s2_wgrad_slab_elems": (c_size_t, [D]),
+    "fv_conv2d_s2_wgrad_bias_slab_elems": (c_size_t, [D]),
+    "fv_conv2d_s2_bwd_weight": (c_int, [D, c_int, c_int, P, P, c_int, P, P, P]),
+    "fv_conv2d_s2_wgrad_reduce": (c_int, [D, P, P, P, P, P]),
+    "fv_in_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "fv_in_stats": (c_int, [c_int, P, c_int, c_int, c_int, c_int, c_float, P, P, P, P]),
+    "fv_in_act_fwd": (c_int, [c_int, P, c_int, c_int, c_int, c_int, P, P, P, P, c_float, P, P]),
+    "fv_in_act_bwd_reduce": (c_int, [c_int, P, P, c_int, c_int, c_int, c_int, P, P, P, P, c_float, P, P, P, P, P]),
+    "fv_in_act_bwd_apply": (c_int, [c_int, P, P, c_int, c_int, c_int, c_int, P, P, P, P, c_float, P, P, P]),
+    "fv_disc_input_fwd": (c_int, [c_int, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
 }
 
 _lib = None

@@ -40,6 +40,11 @@ class FaceVAEConfig:
     lr: float = 5e-5          # train.py:34
     betas: Tuple[float, float] = (0.5, 0.999)   # logger.py:60
     syncbn: bool = True       # SyncBatchNorm semantics across ranks (logger.py:55)
+    # adversarial terms (trainer.py:298-303): hinge GAN and feature matching from a patch
+    # discriminator; both 0 = the plain VAE step, no discriminator is built
+    w_G: float = 0.0
+    w_F: float = 0.0
+    disc_down_seq: Tuple[int, ...] = (64, 128, 256, 512)
 
     @staticmethod
     def toy() -> "FaceVAEConfig":

@@ -116,9 +116,18 @@ struct ConvArgs {
 };
 
 // output pixel of tile-space pixel p (identity unless a sub-pixel phase is set)
+// GSUB: the tile space is any H x W image (divisions), not a power-of-two one (lgw, lghw):
+// the phases of the stride-2 conv's data gradient (conv_fwd_kernel S2 == 2)
+template <bool GSUB = false>
 __device__ __forceinline__ int out_pix(const ConvArgs& a, int p) {
   if (!a.sub) return p;
   const int ph = a.sub - 1, pa = ph >> 1, pb = ph & 1;
+  if constexpr (GSUB) {
+    const int hw = a.H * a.W;
+    const int n = p / hw, rem = p - n * hw;
+    const int h = rem / a.W, w = rem - h * a.W;
+    return (n * a.Ho + 2 * h + pa) * a.Wo + 2 * w + pb;
+  }
   const int n = p >> a.lghw, rem = p & ((1 << a.lghw) - 1);
   const int h = rem >> a.lgw, w = rem & ((1 << a.lgw) - 1);
   return (n * a.Ho + 2 * h + pa) * a.Wo + 2 * w + pb;
@@ -195,7 +204,7 @@ __device__ __forceinline__ f32x4 mma(const Frag<float>& a, const Frag<float>& b,
 struct NoMid {
   __device__ void operator()() const {}
 };
-template <typename T, int WN, int WM, int RN, int RM, bool STAGED = false, typename Mid = NoMid>
+template <typename T, int WN, int WM, int RN, int RM, bool STAGED = false, typename Mid = NoMid, bool GSUB = false>
 __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x4 (&acc)[RN][RM], char* smem, int co0, int p0,
                                               int tm, int wn, int wm, int lane, int tid, Mid mid = Mid{}) {
   constexpr bool kMid = !std::is_same<Mid, NoMid>::value;
@@ -222,7 +231,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x4 (&acc)[RN
         rpre[it] = make_uint4(0, 0, 0, 0);
         if (idx < BM * SCPR && tp < a.P && co < a.Cout)
           rpre[it] = *reinterpret_cast<const uint4*>(reinterpret_cast<const bf16*>(a.res) +
-                                                      (long)out_pix(a, tp) * a.ldy + co);
+                                                      (long)out_pix<GSUB>(a, tp) * a.ldy + co);
       }
     }
   };
@@ -242,7 +251,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x4 (&acc)[RN
     const int loc = wm * RM * 16 + m * 16 + lr;
     const int tp = a.lgtw ? p0 + (loc >> a.lgtw) * a.W + (loc & ((1 << a.lgtw) - 1)) : p0 + loc;
     pv[m] = tp < a.P;
-    pix_of[m] = out_pix(a, tp);
+    pix_of[m] = out_pix<GSUB>(a, tp);
   }
 #pragma unroll
   for (int n = 0; n < RN; ++n) {
@@ -344,7 +353,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x4 (&acc)[RN
         const int tp = a.lgtw ? p0 + (pl >> a.lgtw) * a.W + (pl & ((1 << a.lgtw) - 1)) : p0 + pl;
         const int co = co0 + ch * 8;
         if (tp >= a.P || co >= a.Cout) continue;
-        const int pix = out_pix(a, tp);
+        const int pix = out_pix<GSUB>(a, tp);
         Chunk8<bf16> v;
         v.raw = chunk(it, pl, ch);
         T* yp = reinterpret_cast<T*>(a.y) + (long)pix * a.ldy + co;
@@ -385,7 +394,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x4 (&acc)[RN
       const int tp = a.lgtw ? p0 + (pl >> a.lgtw) * a.W + (pl & ((1 << a.lgtw) - 1)) : p0 + pl;
       const int co = co0 + ch * 8;
       if (tp >= a.P || co >= a.Cout) continue;
-      const int pix = out_pix(a, tp);
+      const int pix = out_pix<GSUB>(a, tp);
       Chunk8<bf16> v;
       v.raw = chunk(it, pl, ch);
       T* yp = reinterpret_cast<T*>(a.y) + (long)pix * a.ldy + co;
@@ -470,7 +479,12 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x4 (&acc)[RN
   }
 }
 
-template <typename T, int KS, int WN, int WM, int RN, int RM, bool PRO, bool UPS>
+// S2 (stride-2 3x3 conv, padding 1; fv_conv2d_s2_*): 1 = forward, tile space = the H x W output,
+// input (Hin, Win) = (2H, 2W) read at 2 * out + tap - 1; 2 = one phase (a.sub = 1 + 2 pa + pb) of
+// its data gradient, a transposed conv: tile space = the H x W gradient image dy (the input),
+// tile pixel (h, w) stores dx pixel (2h + pa, 2w + pb) and gathers only the phase's live taps,
+// (1 + pa) x (1 + pb) of them at offsets {0, +1} (weights: weight_prep_s2t_kernel).
+template <typename T, int KS, int WN, int WM, int RN, int RM, bool PRO, bool UPS, int S2 = 0>
 __global__ void __launch_bounds__(64 * WN * WM)
 conv_fwd_kernel(ConvArgs a) {
   constexpr int NT = 64 * WN * WM;
@@ -516,12 +530,14 @@ conv_fwd_kernel(ConvArgs a) {
     const bool kin = k < a.K;
     const int tap = k >> a.lgCin;
     const int ci = k & (a.Cin - 1);
-    const int r = tap / KS, s = tap - (tap / KS) * KS;
+    const int sdiv = S2 == 2 ? 1 + ((a.sub - 1) & 1) : KS;      // taps per row
+    const int r = tap / sdiv, s = tap - (tap / sdiv) * sdiv;
     cur_ci = ci;
     okm = 0;
 #pragma unroll
     for (int i = 0; i < CA; ++i) {
-      const int hh = rh[i] + r - PAD, ww = rw[i] + s - PAD;
+      const int hh = S2 == 2 ? rh[i] + r : (S2 == 1 ? 2 * rh[i] : rh[i]) + r - PAD;
+      const int ww = S2 == 2 ? rw[i] + s : (S2 == 1 ? 2 * rw[i] : rw[i]) + s - PAD;
       bool ok = kin && rv[i];
       int hs, ws;
       if constexpr (UPS) {
@@ -618,7 +634,7 @@ conv_fwd_kernel(ConvArgs a) {
     __syncthreads();
   }
 
-  conv_epilogue<T, WN, WM, RN, RM>(a, acc, smem, co0, p0, tm, wn, wm, lane, tid);
+  conv_epilogue<T, WN, WM, RN, RM, false, NoMid, S2 == 2>(a, acc, smem, co0, p0, tm, wn, wm, lane, tid);
 }
 
 // ----------------------------------------------------------------------------------------
@@ -2582,7 +2598,8 @@ __device__ __forceinline__ void colfrag(const char* base, int cbase, int lane, F
   }
 }
 
-template <typename T, int KS, int WK, int WC, int RK, int RC, bool PRO, bool UPS>
+// S2 = 1: the stride-2 3x3 conv (pixels = the H x W output, x read at 2 * out + tap - 1)
+template <typename T, int KS, int WK, int WC, int RK, int RC, bool PRO, bool UPS, int S2 = 0>
 __global__ void __launch_bounds__(64 * WK * WC)
 conv_wgrad_kernel(WgArgs a) {
   constexpr int NT = 64 * WK * WC;
@@ -2635,7 +2652,7 @@ conv_wgrad_kernel(WgArgs a) {
       bool ok = kin && (q < PX * KCH) && pix < a.P;
       int n = pix / HW, r2 = pix - n * HW;
       int h = r2 / a.W, w = r2 - h * a.W;
-      int hh = h + rr - PAD, ww = w + ss - PAD;
+      int hh = (S2 ? 2 * h : h) + rr - PAD, ww = (S2 ? 2 * w : w) + ss - PAD;
       int hs, ws;
       if constexpr (UPS) {
         ok = ok && hh >= 0 && hh < a.H && ww >= 0 && ww < a.W;
@@ -4036,6 +4053,31 @@ __global__ void weight_prep_kernel(const float* __restrict__ wp, const float* si
                       smaj);
 }
 
+// Data-gradient weights of the stride-2 3x3 conv (conv_fwd_kernel S2 == 2): four phase images
+// [phase = 2 pa + pb][rows][Kph], Kph = 4 * cin_t (the (1 + pa)(1 + pb) * cin_t live k of a phase
+// first, zeros behind).  dx[2h + pa][2w + pb] = sum of dy[h + r][w + s] W[co][ci][kr][kc] over
+// the taps with 2 (h + r) + kr - 1 = 2h + pa: an even row (pa = 0) meets only kr = 1 at r = 0,
+// an odd row kr = 2 at r = 0 and kr = 0 at r = 1; columns alike.
+template <typename T>
+__global__ void weight_prep_s2t_kernel(const float* __restrict__ wp, const float* sigma, T* wt, int rows, int Kph,
+                                       int cout, int cin_valid, int lgC) {
+  const int total = 4 * rows * Kph;
+  const float inv = sigma ? 1.f / sigma[0] : 1.f;
+  for (int e = blockIdx.x * (int)blockDim.x + threadIdx.x; e < total; e += gridDim.x * (int)blockDim.x) {
+    const int ph = e / (rows * Kph), q = e - ph * rows * Kph;
+    const int row = q / Kph, k = q - row * Kph;
+    const int pa = ph >> 1, pb = ph & 1;
+    const int tap = k >> lgC, c = k & ((1 << lgC) - 1);
+    const int r = tap >> pb, s = tap & pb;
+    float v = 0.f;
+    if (tap < (1 + pa) * (1 + pb) && row < cin_valid && c < cout) {
+      const int kr = pa ? 2 - 2 * r : 1, kc = pb ? 2 - 2 * s : 1;
+      v = wp[(((long)c * cin_valid + row) * 3 + kr) * 3 + kc];
+    }
+    wt[e] = Elt<T>::from_f(v * inv);
+  }
+}
+
 // both layouts in one launch: blocks [0, nb1) write wk, the rest wt
 struct WPrepJob { void* out; int rows, Kpad, lgCin, K, transposed, nb, smaj; };
 template <typename T>
@@ -4932,6 +4974,63 @@ int launch_wg_ks(const WgArgs& a, const WgPlan& t, int pro, int ups, int nblk, h
   return launch_wg_t<T, KS, 4, 1, 2, 1>(a, pro, ups, nblk, s);
 }
 
+// stride-2 3x3 conv on the generic kernels: forward (S2 = 1) / one data-gradient phase (S2 = 2)
+template <typename T, int S2>
+void launch_s2_fwd(const ConvArgs& a, FwdTile t, int nblk, hipStream_t s) {
+  dim3 g(nblk);
+  if (t.bn == 128) hipLaunchKernelGGL((conv_fwd_kernel<T, 3, 2, 2, 4, 4, false, false, S2>), g, dim3(256), 0, s, a);
+  else if (t.bn == 64) hipLaunchKernelGGL((conv_fwd_kernel<T, 3, 2, 2, 2, 4, false, false, S2>), g, dim3(256), 0, s, a);
+  else if (t.bn == 32) hipLaunchKernelGGL((conv_fwd_kernel<T, 3, 2, 2, 1, 4, false, false, S2>), g, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((conv_fwd_kernel<T, 3, 1, 4, 1, 2, false, false, S2>), g, dim3(256), 0, s, a);
+}
+template <typename T>
+void launch_s2_wg(const WgArgs& a, const WgPlan& t, int nblk, hipStream_t s) {
+  dim3 g(nblk), b(256);
+  if (t.bc == 128) hipLaunchKernelGGL((conv_wgrad_kernel<T, 3, 2, 2, 4, 4, false, false, 1>), g, b, 0, s, a);
+  else if (t.bc == 64) hipLaunchKernelGGL((conv_wgrad_kernel<T, 3, 2, 2, 4, 2, false, false, 1>), g, b, 0, s, a);
+  else hipLaunchKernelGGL((conv_wgrad_kernel<T, 3, 4, 1, 2, 1, false, false, 1>), g, b, 0, s, a);
+}
+// the weight gradient's plan: the generic kernel's tiles (plan_wgrad's fp32 branch) for both dtypes
+WgPlan plan_wgrad_s2(const fv_conv_desc* d) {
+  WgPlan p{};
+  const int K = 9 * d->cin;
+  const long P = (long)d->n * d->h * d->w;
+  p.bc = d->cout > 64 ? 128 : (d->cout > 16 ? 64 : 16);
+  p.bkt = 128;
+  p.px = 32;
+  p.ntk = fv_cdiv(K, p.bkt);
+  p.ntc = fv_cdiv(d->cout, p.bc);
+  p.nsteps = fv_cdiv(P, p.px);
+  const int ntile = p.ntk * p.ntc;
+  int ns = 768 / ntile;
+  if (ns < 1) ns = 1;
+  if (ns > p.nsteps) ns = p.nsteps;
+  p.sps = fv_cdiv(p.nsteps, ns);
+  p.nsplit = fv_cdiv(p.nsteps, p.sps);
+  p.KW = p.ntk * p.bkt;
+  p.CW = p.ntc * p.bc;
+  return p;
+}
+// descriptor and size checks shared by the fv_conv2d_s2_* entries
+int check_s2(const fv_conv_desc* d) {
+  int st = check_desc(d);
+  if (st) return st;
+  if (d->ksize != 3 || d->upsample || d->pro_act || d->epi_sigmoid || d->out_nchw_f32) {
+    fv_set_error("stride-2 conv: 3x3, no upsample / BN prologue / sigmoid / NCHW output");
+    return FV_E_UNSUPPORTED;
+  }
+  FV_REQUIRE(4L * d->n * d->h * d->w < (1L << 31), "stride-2 conv: more than 2^31 input pixels");
+  return FV_OK;
+}
+int check_s2_in(const fv_conv_desc* d, int in_h, int in_w) {
+  if (in_h != 2 * d->h || in_w != 2 * d->w) {
+    fv_set_error("stride-2 conv: the input must be (2h, 2w) = %d x %d for a %d x %d output, odd sizes are not "
+                 "supported (got %d x %d)", 2 * d->h, 2 * d->w, d->h, d->w, in_h, in_w);
+    return FV_E_UNSUPPORTED;
+  }
+  return FV_OK;
+}
+
 template <typename T>
 int launch_wg(const WgArgs& a, int ks, const WgPlan& t, int pro, int ups, int nblk, hipStream_t s) {
   switch (ks) {
@@ -5813,6 +5912,156 @@ int fv_conv2d_wgrad_reduce(const fv_conv_desc* d, const float* slab, const float
                      bias_slab, dw_param, db, t.nsplit, t.CW, t.KW, K, d->cout, d->cin_valid, pk ? 2 : fv_ilog2(d->cin),
                      d->ksize, nb_main, pk ? 8 : d->ksize);
   return fv_check_launch("wgrad_reduce");
+}
+
+// ---- stride-2 3x3 conv, padding 1 (the discriminator's down blocks, models.py:1120-1124) ----
+size_t fv_conv2d_s2_wk_elems(const fv_conv_desc* d) {
+  if (check_s2(d) != FV_OK) return 0;
+  return (size_t)wrows(d->cout) * kpad_of(3, d->cin);
+}
+
+size_t fv_conv2d_s2_wt_elems(const fv_conv_desc* d) {
+  if (check_s2(d) != FV_OK) return 0;
+  return (size_t)4 * wrows(d->cin) * 4 * pad_pow2_8(d->cout);
+}
+
+int fv_conv2d_s2_weight_prep(const fv_conv_desc* d, const float* w_param, const float* sigma, void* wk, void* wt,
+                             void* stream) {
+  int st = check_s2(d);
+  if (st) return st;
+  FV_REQUIRE(w_param, "null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  if (wk) {
+    const int rows = wrows(d->cout), Kp = kpad_of(3, d->cin);
+    const int nb = (int)std::min<long>(fv_cdiv((long)rows * Kp, 256), 4096);
+    if (d->dtype == FV_BF16)
+      hipLaunchKernelGGL(weight_prep_kernel<bf16>, dim3(nb), dim3(256), 0, s, w_param, sigma, (bf16*)wk, rows, Kp,
+                         d->cout, d->cin_valid, fv_ilog2(d->cin), 3, 9 * d->cin, 0, 0);
+    else
+      hipLaunchKernelGGL(weight_prep_kernel<float>, dim3(nb), dim3(256), 0, s, w_param, sigma, (float*)wk, rows, Kp,
+                         d->cout, d->cin_valid, fv_ilog2(d->cin), 3, 9 * d->cin, 0, 0);
+    if ((st = fv_check_launch("s2_weight_prep"))) return st;
+  }
+  if (wt) {
+    const int cin_t = pad_pow2_8(d->cout);
+    const int rows = wrows(d->cin), Kph = 4 * cin_t;
+    const int nb = (int)std::min<long>(fv_cdiv(4L * rows * Kph, 256), 4096);
+    if (d->dtype == FV_BF16)
+      hipLaunchKernelGGL(weight_prep_s2t_kernel<bf16>, dim3(nb), dim3(256), 0, s, w_param, sigma, (bf16*)wt, rows, Kph,
+                         d->cout, d->cin_valid, fv_ilog2(cin_t));
+    else
+      hipLaunchKernelGGL(weight_prep_s2t_kernel<float>, dim3(nb), dim3(256), 0, s, w_param, sigma, (float*)wt, rows,
+                         Kph, d->cout, d->cin_valid, fv_ilog2(cin_t));
+    if ((st = fv_check_launch("s2_weight_prep_t"))) return st;
+  }
+  return FV_OK;
+}
+
+int fv_conv2d_s2_fwd(const fv_conv_desc* d, int in_h, int in_w, const void* x, const void* wk, const float* bias,
+                     void* y, void* stream) {
+  int st = check_s2(d);
+  if (st) return st;
+  if ((st = check_s2_in(d, in_h, in_w))) return st;
+  FV_REQUIRE(x && wk && y, "null pointer");
+  FV_REQUIRE(d->ldy >= d->cout, "ldy < cout");
+  ConvArgs a{};
+  const FwdTile t = fwd_tile(d->cout);
+  a.x = x; a.w = wk; a.bias = bias; a.y = y;
+  a.N = d->n; a.H = d->h; a.W = d->w; a.Hin = in_h; a.Win = in_w;
+  a.P = d->n * d->h * d->w;
+  a.Cin = d->cin; a.lgCin = fv_ilog2(d->cin);
+  a.Cout = d->cout; a.ldy = d->ldy;
+  a.K = 9 * d->cin; a.Kpad = kpad_of(3, d->cin); a.nks = a.Kpad / BK;
+  a.ntn = fv_cdiv(d->cout, t.bn);
+  FV_REQUIRE((long)a.ntn * t.bn <= wrows(d->cout), "stride-2 conv: weight rows");
+  const int nblk = a.ntn * fv_cdiv(a.P, t.bm);
+  if (d->dtype == FV_BF16) launch_s2_fwd<bf16, 1>(a, t, nblk, (hipStream_t)stream);
+  else launch_s2_fwd<float, 1>(a, t, nblk, (hipStream_t)stream);
+  return fv_check_launch("conv2d_s2_fwd");
+}
+
+int fv_conv2d_s2_bwd_data(const fv_conv_desc* d, int in_h, int in_w, const void* dy, int ldy_dy, const void* wt,
+                          void* dx, void* stream) {
+  int st = check_s2(d);
+  if (st) return st;
+  if ((st = check_s2_in(d, in_h, in_w))) return st;
+  FV_REQUIRE(dy && wt && dx, "null pointer");
+  const int cin_t = pad_pow2_8(d->cout);
+  FV_REQUIRE(ldy_dy == cin_t, "stride-2 bwd_data: dy channel stride must be %d (got %d)", cin_t, ldy_dy);
+  const FwdTile t = fwd_tile(d->cin);
+  const int rows = wrows(d->cin);
+  const long wphase = (long)rows * 4 * cin_t;
+  const size_t es = d->dtype == FV_BF16 ? 2 : 4;
+  for (int ph = 0; ph < 4; ++ph) {
+    const int nt = (1 + (ph >> 1)) * (1 + (ph & 1));
+    ConvArgs a{};
+    a.x = dy; a.w = (const char*)wt + (size_t)ph * wphase * es; a.y = dx;
+    a.N = d->n; a.H = d->h; a.W = d->w; a.Hin = d->h; a.Win = d->w;
+    a.Ho = in_h; a.Wo = in_w;
+    a.P = d->n * d->h * d->w;
+    a.sub = 1 + ph;
+    a.Cin = cin_t; a.lgCin = fv_ilog2(cin_t);
+    a.Cout = d->cin; a.ldy = d->cin;         // every (padded) input channel; padded ones come out 0
+    a.K = nt * cin_t; a.Kpad = 4 * cin_t; a.nks = fv_cdiv(a.K, BK);
+    a.ntn = fv_cdiv(d->cin, t.bn);
+    FV_REQUIRE((long)a.ntn * t.bn <= rows && a.nks * BK <= a.Kpad, "stride-2 bwd_data: weight image");
+    const int nblk = a.ntn * fv_cdiv(a.P, t.bm);
+    if (d->dtype == FV_BF16) launch_s2_fwd<bf16, 2>(a, t, nblk, (hipStream_t)stream);
+    else launch_s2_fwd<float, 2>(a, t, nblk, (hipStream_t)stream);
+  }
+  return fv_check_launch("conv2d_s2_bwd_data");
+}
+
+size_t fv_conv2d_s2_wgrad_slab_elems(const fv_conv_desc* d) {
+  if (check_s2(d) != FV_OK) return 0;
+  const WgPlan p = plan_wgrad_s2(d);
+  return (size_t)p.nsplit * p.CW * p.KW;
+}
+
+size_t fv_conv2d_s2_wgrad_bias_slab_elems(const fv_conv_desc* d) {
+  if (check_s2(d) != FV_OK) return 0;
+  const WgPlan p = plan_wgrad_s2(d);
+  return (size_t)p.nsplit * p.CW;
+}
+
+int fv_conv2d_s2_bwd_weight(const fv_conv_desc* d, int in_h, int in_w, const void* x, const void* dy, int ldy_dy,
+                            float* slab, float* bias_slab, void* stream) {
+  int st = check_s2(d);
+  if (st) return st;
+  if ((st = check_s2_in(d, in_h, in_w))) return st;
+  FV_REQUIRE(x && dy && slab, "null pointer");
+  FV_REQUIRE(ldy_dy % 8 == 0 && ldy_dy >= d->cout, "wgrad: dy channel stride must be a multiple of 8 >= cout");
+  const WgPlan t = plan_wgrad_s2(d);
+  WgArgs a{};
+  a.x = x; a.dy = dy; a.slab = slab; a.bslab = bias_slab;
+  a.N = d->n; a.H = d->h; a.W = d->w; a.Hin = in_h; a.Win = in_w;
+  a.P = d->n * d->h * d->w;
+  a.Cin = d->cin; a.lgCin = fv_ilog2(d->cin);
+  a.K = 9 * d->cin;
+  a.ntk = t.ntk; a.KW = t.KW;
+  a.Cout = d->cout; a.ldd = ldy_dy;
+  a.ntc = t.ntc; a.CW = t.CW;
+  a.nsteps = t.nsteps;
+  a.steps_per_split = t.sps;
+  const int nblk = t.ntk * t.ntc * t.nsplit;
+  if (d->dtype == FV_BF16) launch_s2_wg<bf16>(a, t, nblk, (hipStream_t)stream);
+  else launch_s2_wg<float>(a, t, nblk, (hipStream_t)stream);
+  return fv_check_launch("conv2d_s2_bwd_weight");
+}
+
+int fv_conv2d_s2_wgrad_reduce(const fv_conv_desc* d, const float* slab, const float* bias_slab, float* dw_param,
+                              float* db, void* stream) {
+  int st = check_s2(d);
+  if (st) return st;
+  FV_REQUIRE(slab && dw_param, "null pointer");
+  FV_REQUIRE(!db || bias_slab, "db needs the bias slab");
+  const WgPlan t = plan_wgrad_s2(d);
+  const int K = 9 * d->cin;
+  const int nb_main = fv_cdiv((long)d->cout * K, 64);
+  const int nb_bias = db ? fv_cdiv(d->cout, 64) : 0;
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(nb_main + nb_bias), dim3(256), 0, (hipStream_t)stream, slab, bias_slab,
+                     dw_param, db, t.nsplit, t.CW, t.KW, K, d->cout, d->cin_valid, fv_ilog2(d->cin), 3, nb_main, 3);
+  return fv_check_launch("s2_wgrad_reduce");
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 """Loss modules with the reference call signatures (losses.py of Luh1124/face-vae)."""
 from __future__ import annotations
 
+import torch
 from torch import nn
 
 from . import ops
@@ -26,6 +27,40 @@ class L1Loss(nn.Module):
 
     def forward(self, input, target):
         return ops.l1_loss(input, target)
+
+
+class GANLoss(nn.Module):
+    """Hinge GAN loss (losses.py:154-179) on the discriminator's [N, 1, h, w] fp32 logits (a few
+    KB: plain torch ops).  GANLoss()(dis_output, t_real, dis_update):
+      discriminator update, real:  -mean(min(x - 1, 0))
+      discriminator update, fake:  -mean(min(-x - 1, 0))
+      generator update:            -mean(x)"""
+
+    def forward(self, dis_output, t_real, dis_update=True):
+        x = dis_output.float()
+        if not dis_update:
+            return -torch.mean(x)
+        v = x - 1 if t_real else -x - 1
+        return -torch.mean(torch.clamp(v, max=0))
+
+
+class FeatureMatchingLoss(nn.Module):
+    """losses.py:182-195, called as FeatureMatchingLoss()(fake_features, real_features) with the
+    discriminator's feature lists.  The reference loops `fake_features[i][j]` over the SAMPLES j of
+    layer i and adds mean|.| of each sample's slice with weight 1 / n_layers; the per-sample
+    means of equal-sized slices sum to B times the layer's mean, so the value is
+    (B / n_layers) * sum_i mean|fake_i - real_i.detach()|, not the plain mean.  It is computed
+    in that closed form: one L1 kernel pass (ops.l1_loss) per layer."""
+
+    def forward(self, fake_features, real_features):
+        num_d = len(fake_features)
+        loss = None
+        for f, r in zip(fake_features, real_features):
+            if not f.is_cuda:
+                raise RuntimeError("facevae_amd ops run on the GPU only (HIP); got a CPU tensor")
+            t = ops.l1_loss(f, r.detach()) * (f.shape[0] / num_d)
+            loss = t if loss is None else loss + t
+        return loss
 
 
 from .perceptual import PerceptualLoss  # noqa: E402,F401  (losses.py:123-151)

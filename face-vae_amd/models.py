@@ -104,6 +104,46 @@ class Generator(_Block):
         return self.forward_2d(fs, occlusion)
 
 
+class Discriminator(_Block):
+    """Patch discriminator (models.py:1114-1139): ConvBlock2D "CNA" with instance norm and
+    LeakyReLU(0.2), stride 2 for all but the last of them, then a "CN" 3x3 conv to one channel.
+    forward(x, kp) -> (output [N, 1, h, w] NCHW fp32, features = the outputs of the instance-norm
+    blocks).  The input is the image with K keypoint heatmaps (kp detached, kp[..., :2] used)
+    appended; kp may be None when K == 0.  Each top-level forward runs one power iteration per
+    spectral-normed conv in training mode, as torch's spectral_norm does."""
+
+    def __init__(self, use_weight_norm=True, down_seq=(64, 128, 256, 512), K=15):
+        super().__init__()
+        down_seq = list(down_seq)
+        if 3 + K > 32:
+            raise NotImplementedError("facevae_amd Discriminator: 3 + K <= 32")
+        layers = [ConvBlock2D("CNA", 3 + K, down_seq[0], 3, 2, 1, use_weight_norm, "instance", "leakyrelu")]
+        layers.extend(ConvBlock2D("CNA", down_seq[i], down_seq[i + 1], 3, 2 if i < len(down_seq) - 2 else 1, 1,
+                                  use_weight_norm, "instance", "leakyrelu") for i in range(len(down_seq) - 1))
+        layers.append(ConvBlock2D("CN", down_seq[-1], 1, 3, 1, 1, use_weight_norm, activation_type="none"))
+        self.layers = nn.ModuleList(layers)
+        self.K = K
+        for blk in self.layers:
+            # real and fake forwards meet in one backward pass: their spectral-norm terms are
+            # applied per forward, not batched at the end of backward (ops._sn_defer_ok)
+            blk.conv._fv_sn_nodefer = True
+
+    def forward(self, x, kp=None):
+        if not x.is_cuda:
+            raise RuntimeError("facevae_amd ops run on the GPU only (HIP); got a CPU tensor")
+        if self.K > 0 and kp is None:
+            raise ValueError("Discriminator: keypoints are required when K > 0")
+        if kp is not None and kp.shape[1] != self.K:
+            raise ValueError(f"Discriminator: expected {self.K} keypoints, got {kp.shape[1]}")
+        _batched_weight_prep(self, x.device)
+        h = ops.DiscInputFn.apply(x, kp, self.K, ops.storage(self.compute_dtype()))
+        res = []
+        for layer in self.layers:
+            h = layer(h)
+            res.append(h)
+        return res[-1], res[:-1]
+
+
 class FaceVAE(_Block):
     """AFE 2-D trunk -> [mu | logstd] split + reparameterisation -> Generator 2-D trunk.
 

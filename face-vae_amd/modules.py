@@ -70,6 +70,24 @@ class _BatchNorm(nn.Module):
         return f"{self.num_features}, eps={self.eps}, momentum={self.momentum}"
 
 
+class _InstanceNorm(nn.Module):
+    """nn.InstanceNorm2d(C, affine=True) parameter holder (modules.py:21): `weight`, `bias`, no
+    buffers (no running statistics, so train and eval are the same computation)."""
+
+    def __init__(self, num_features, eps=1e-5):
+        super().__init__()
+        self.num_features, self.eps = num_features, eps
+        self.weight = nn.Parameter(torch.ones(num_features))
+        self.bias = nn.Parameter(torch.zeros(num_features))
+
+    def extra_repr(self):
+        return f"{self.num_features}, eps={self.eps}, affine=True"
+
+
+class _Identity(nn.Module):
+    """nn.Identity stand-in (activation_type="none"): no parameters."""
+
+
 class _Act(nn.Module):
     def __init__(self, kind):
         super().__init__()
@@ -116,11 +134,21 @@ class _Block(nn.Module):
 
 class ConvBlock2D(_Block):
     """_ConvBlock (modules.py:8-49).  Patterns "CNA" (BN on the output) and "NAC" (BN on the
-    input) are fused into one kernel chain; stride must be 1 and padding kernel_size // 2."""
+    input) are fused into one kernel chain; stride must be 1 and padding kernel_size // 2.
+
+    The patch discriminator's blocks (models.py:1120-1127) are accepted too: "CNA" with
+    activation_type "instance" (conv -> InstanceNorm2d(affine) -> act) at stride 1 or at stride 2
+    with a 3x3 kernel and padding 1 (ops.ConvINActFn), and "CN" with activation_type "none" (a
+    plain conv, ops.ConvFn)."""
 
     def __init__(self, pattern, in_channels, out_channels, kernel_size, stride, padding, use_weight_norm,
                  activation_type="batch", nonlinearity_type="relu"):
         super().__init__()
+        self.stride = stride
+        if activation_type in ("instance", "none"):
+            self._init_disc(pattern, in_channels, out_channels, kernel_size, stride, padding, use_weight_norm,
+                            activation_type, nonlinearity_type)
+            return
         if stride != 1 or padding != kernel_size // 2:
             raise NotImplementedError("facevae_amd ConvBlock2D: stride 1, 'same' padding only")
         if activation_type != "batch":
@@ -140,7 +168,41 @@ class ConvBlock2D(_Block):
         self.upsample = False
         self.pool = False
 
+    def _init_disc(self, pattern, in_channels, out_channels, kernel_size, stride, padding, use_weight_norm,
+                   activation_type, nonlinearity_type):
+        if not ((stride == 1 and padding == kernel_size // 2) or (stride, kernel_size, padding) == (2, 3, 1)):
+            raise NotImplementedError("facevae_amd ConvBlock2D: stride 1 with 'same' padding, or stride 2 with a "
+                                      "3x3 kernel and padding 1")
+        if (activation_type, pattern) not in (("instance", "CNA"), ("none", "CN")):
+            raise NotImplementedError(f"facevae_amd ConvBlock2D: activation_type={activation_type!r} with pattern "
+                                      f"{pattern!r} (supported: 'instance' with 'CNA', 'none' with 'CN')")
+        if activation_type == "none" and stride != 1:
+            raise NotImplementedError("facevae_amd ConvBlock2D: the 'CN' block is stride 1 only")
+        if activation_type == "instance" and not (ops.is_pow2_8(out_channels) and out_channels <= 512):
+            raise NotImplementedError("facevae_amd ConvBlock2D: instance norm needs a power-of-two channel count in "
+                                      "[8, 512]")
+        self.pattern = "CIA" if activation_type == "instance" else "CN"
+        # same RNG draws as the reference: nn.Conv2d.reset_parameters, then spectral norm's u, v;
+        # InstanceNorm2d / Identity draw nothing
+        mappings = {"C": _Conv(in_channels, out_channels, kernel_size, use_weight_norm),
+                    "N": _InstanceNorm(out_channels) if activation_type == "instance" else _Identity()}
+        if "A" in pattern:
+            mappings["A"] = _Act(nonlinearity_type)
+        self.layers = nn.Sequential(*[mappings[c] for c in pattern])
+        _ref(self, "conv", mappings["C"])
+        _ref(self, "bn", mappings["N"])
+        if "A" in pattern:
+            _ref(self, "act", mappings["A"])
+            self.slope = self.act.slope
+        self.upsample = False
+        self.pool = False
+
     def forward(self, x):
+        if self.pattern == "CIA":
+            return ops.ConvINActFn.apply(x, self.conv.weight_param(), self.conv.bias, self.bn.weight, self.bn.bias, self)
+        if self.pattern == "CN":
+            return ops.ConvFn.apply(x, self.conv.weight_param(), self.conv.bias, self.conv,
+                                    ops.storage(self.compute_dtype()), 0)
         if self.pattern == "CNA":
             z = ops.ConvBNActFn.apply(x, self.conv.weight_param(), self.conv.bias, self.bn.weight, self.bn.bias, self)
             holder = getattr(self, "_fv_holder", None)

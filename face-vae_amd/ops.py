@@ -537,6 +537,10 @@ _SN_DEFER = {"items": [], "armed": False, "stream": None}
 def _sn_defer_ok(cs: ConvState) -> bool:
     if not _SN_BATCH or cs.w.grad is not None:
         return False
+    if getattr(cs.conv, "_fv_sn_nodefer", False):
+        # a conv run more than once per backward pass (the discriminator: real and fake
+        # forwards, each with its own (u, v, sigma) snapshot) applies each term at once
+        return False
     if torch.distributed.is_available() and torch.distributed.is_initialized() \
             and torch.distributed.get_world_size() > 1:
         return False
@@ -1132,6 +1136,176 @@ class ConvFn(torch.autograd.Function):
         dxb, dw, db = conv_backward(cs, xb, dpre, ldd, need_dx=ctx.needs_input_grad[0])
         dx = from_nhwc(dxb, x) if dxb is not None else None
         return dx, dw, db, None, None, None
+
+
+# ----------------------------------------------------------------------------------------
+# patch discriminator blocks (models.py:1114-1139): stride-2 3x3 conv, instance norm
+# ----------------------------------------------------------------------------------------
+
+class S2ConvState:
+    """ConvState of a stride-2 3x3 conv (padding 1): d.h / d.w are the OUTPUT size, the weights
+    are prepared by fv_conv2d_s2_weight_prep (generic forward image + the data gradient's four
+    phase images).  Not batched by WPrepBatch (the phase layout is this conv's own)."""
+
+    def __init__(self, conv, d, in_hw, dtype, device, training, need_wt):
+        self.conv, self.d, self.in_hw = conv, d, in_hw
+        w = conv.weight_param()
+        if w.dtype != F32 or not w.is_contiguous():
+            raise RuntimeError("conv weights must be contiguous fp32")
+        self.w = w
+        self.sigma = None
+        self.fp8 = False
+        if conv.sn:
+            pre = getattr(conv, "_sn_pre", None)
+            if pre is not None:           # computed by the model's SNBatch for this forward
+                self.sigma, self.u, self.v = pre
+                conv._sn_pre = None
+            else:
+                self.sigma = spectral_norm_fwd(w, conv.weight_u, conv.weight_v, training)
+                self.u = conv.weight_u.clone()
+                self.v = conv.weight_v.clone()
+        conv._fv_desc = conv._fv_prep = conv._fv_desc8 = conv._fv_prep8 = None
+        self.wk = _empty(query("fv_conv2d_s2_wk_elems", ctypes.byref(d)), dtype, device)
+        self.wt = _empty(query("fv_conv2d_s2_wt_elems", ctypes.byref(d)), dtype, device) if need_wt else None
+        call("fv_conv2d_s2_weight_prep", ctypes.byref(d), ptr(w), ptr(self.sigma), ptr(self.wk), ptr(self.wt), stream())
+
+    def release(self):
+        self.wk = None
+
+
+def conv_s2_forward(cs: S2ConvState, x, bias, y):
+    d = cs.d
+    _timed("fwd", d, lambda: call("fv_conv2d_s2_fwd", ctypes.byref(d), cs.in_hw[0], cs.in_hw[1], ptr(x), ptr(cs.wk),
+                                  ptr(bias), ptr(y), stream()))
+
+
+def conv_s2_backward(cs: S2ConvState, x, dy, need_dx=True, need_db=True):
+    """-> (dx [N, cin, 2h, 2w] NHWC or None, dW (param layout, spectral-norm term applied), db)."""
+    d = cs.d
+    dev = dy.device
+    ih, iw = cs.in_hw
+    slab = _empty(query("fv_conv2d_s2_wgrad_slab_elems", ctypes.byref(d)), F32, dev)
+    bslab = _empty(query("fv_conv2d_s2_wgrad_bias_slab_elems", ctypes.byref(d)), F32, dev) if need_db else None
+    _timed("wgrad", d, lambda: call("fv_conv2d_s2_bwd_weight", ctypes.byref(d), ih, iw, ptr(x), ptr(dy), d.cout,
+                                    ptr(slab), ptr(bslab), stream()))
+    dw = torch.empty_like(cs.w)
+    db = torch.empty(d.cout, dtype=F32, device=dev) if need_db else None
+    call("fv_conv2d_s2_wgrad_reduce", ctypes.byref(d), ptr(slab), ptr(bslab), ptr(dw), ptr(db), stream())
+    if cs.conv.sn:
+        spectral_norm_bwd(cs.w, dw, cs.u, cs.v, cs.sigma)
+    dx = None
+    if need_dx:
+        dx = torch.empty((d.n, d.cin, ih, iw), dtype=dy.dtype, device=dev, memory_format=CL)
+        _timed("dgrad", d, lambda: call("fv_conv2d_s2_bwd_data", ctypes.byref(d), ih, iw, ptr(dy), d.cout, ptr(cs.wt),
+                                        ptr(dx), stream()))
+    return dx, dw, db
+
+
+def in_act_forward(y, gamma, beta, slope, eps):
+    """Instance norm (affine) + LeakyReLU of the NHWC tensor y -> (z, mean [N, C], invstd [N, C])."""
+    N, C, H, W = y.shape
+    dev = y.device
+    dc = L.dtype_code(y.dtype)
+    ws = _empty(query("fv_in_ws_bytes", N, H, W, C) // 8, F64, dev)
+    mean = torch.empty((N, C), dtype=F32, device=dev)
+    invstd = torch.empty((N, C), dtype=F32, device=dev)
+    call("fv_in_stats", dc, ptr(y), N, H, W, C, float(eps), ptr(mean), ptr(invstd), ptr(ws), stream())
+    z = torch.empty((N, C, H, W), dtype=y.dtype, device=dev, memory_format=CL)
+    call("fv_in_act_fwd", dc, ptr(y), N, H, W, C, ptr(mean), ptr(invstd), ptr(gamma), ptr(beta), float(slope), ptr(z),
+         stream())
+    return z, mean, invstd
+
+
+def in_act_backward(dz, y, mean, invstd, gamma, beta, slope, need_dx=True):
+    """-> (dy of the norm input or None, dgamma, dbeta); fixed-order sums (bit-reproducible)."""
+    N, C, H, W = y.shape
+    dev = y.device
+    dc = L.dtype_code(y.dtype)
+    ws = _empty(query("fv_in_ws_bytes", N, H, W, C) // 8, F64, dev)
+    dg = torch.empty(C, dtype=F32, device=dev)
+    dbt = torch.empty(C, dtype=F32, device=dev)
+    k = torch.empty((N, 2, C), dtype=F32, device=dev)
+    call("fv_in_act_bwd_reduce", dc, ptr(dz), ptr(y), N, H, W, C, ptr(mean), ptr(invstd), ptr(gamma), ptr(beta),
+         float(slope), ptr(dg), ptr(dbt), ptr(k), ptr(ws), stream())
+    dy = None
+    if need_dx:
+        dy = torch.empty((N, C, H, W), dtype=y.dtype, device=dev, memory_format=CL)
+        call("fv_in_act_bwd_apply", dc, ptr(dz), ptr(y), N, H, W, C, ptr(mean), ptr(invstd), ptr(gamma), ptr(beta),
+             float(slope), ptr(k), ptr(dy), stream())
+    return dy, dg, dbt
+
+
+class ConvINActFn(torch.autograd.Function):
+    """Discriminator block: 3x3 conv (stride 1, or stride 2 with padding 1) -> InstanceNorm2d
+    (affine) -> LeakyReLU (ConvBlock2D "CNA" with activation_type "instance").  In fp8 compute
+    mode the block runs bf16."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, gamma, beta, blk):
+        dtype = storage(blk.compute_dtype())
+        conv, norm = blk.conv, blk.bn
+        xb, cin_pad = to_nhwc(x, dtype)
+        N, _, Hi, Wi = x.shape
+        cout = conv.out_channels
+        s2 = blk.stride == 2
+        H, W = ((Hi + 1) // 2, (Wi + 1) // 2) if s2 else (Hi, Wi)
+        d = desc(dtype, N, H, W, cin_pad, conv.in_channels, cout, cout, conv.kernel_size)
+        y = torch.empty((N, cout, H, W), dtype=dtype, device=x.device, memory_format=CL)
+        if s2:
+            cs = S2ConvState(conv, d, (Hi, Wi), dtype, x.device, blk.training, need_wt=ctx.needs_input_grad[0])
+            conv_s2_forward(cs, xb, bias, y)
+        else:
+            cs = ConvState(conv, d, dtype, x.device, blk.training, need_wt=ctx.needs_input_grad[0])
+            conv_forward(cs, xb, bias, y=y)
+        z, mean, invstd = in_act_forward(y, gamma, beta, blk.slope, norm.eps)
+        cs.release()
+        ctx.blk, ctx.cs, ctx.s2, ctx.stats = blk, cs, s2, (mean, invstd)
+        ctx.save_for_backward(x, xb, y)
+        return z
+
+    @staticmethod
+    def backward(ctx, dz):
+        x, xb, y = ctx.saved_tensors
+        blk, cs = ctx.blk, ctx.cs
+        mean, invstd = ctx.stats
+        dz = grad_in(dz, y.dtype)
+        dy, dg, dbt = in_act_backward(dz, y, mean, invstd, blk.bn.weight, blk.bn.bias, blk.slope)
+        if ctx.s2:
+            dxb, dw, db = conv_s2_backward(cs, xb, dy, need_dx=ctx.needs_input_grad[0])
+        else:
+            dxb, dw, db = conv_backward(cs, xb, dy, y.shape[1], need_dx=ctx.needs_input_grad[0])
+        dx = from_nhwc(dxb, x) if dxb is not None else None
+        return dx, dw, db, dg, dbt, None
+
+
+class DiscInputFn(torch.autograd.Function):
+    """Discriminator input (models.py:1131-1132): NHWC [N, pad_pow2(3 + K), H, W] of the compute
+    dtype from the NCHW fp32 image and the (detached) keypoints; only the image has a gradient."""
+
+    @staticmethod
+    def forward(ctx, x, kp, K, dtype):
+        if not x.is_cuda:
+            raise RuntimeError("facevae_amd ops run on the GPU only (HIP); got a CPU tensor")
+        N, C, H, W = x.shape
+        if C != 3:
+            raise ValueError("discriminator input: a 3-channel image expected")
+        cp = pad_pow2(3 + K)
+        x32 = x.detach().float().contiguous()
+        kpc = kp.detach().float().contiguous() if K > 0 else None
+        out = torch.empty((N, cp, H, W), dtype=dtype, device=x.device, memory_format=CL)
+        call("fv_disc_input_fwd", L.dtype_code(dtype), ptr(x32), ptr(kpc), N, H, W, K, kpc.shape[-1] if K > 0 else 0, cp,
+             ptr(out), stream())
+        ctx.shape = (N, H, W, cp)
+        ctx.xdtype = x.dtype
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        N, H, W, cp = ctx.shape
+        g = g.contiguous(memory_format=CL)
+        dx = torch.empty((N, 3, H, W), dtype=F32, device=g.device)
+        call("fv_nhwc_to_nchw", L.dtype_code(g.dtype), ptr(g), N, 3, H * W, cp, ptr(dx), stream())
+        return dx.to(ctx.xdtype), None, None, None
 
 
 class ReparamFn(torch.autograd.Function):

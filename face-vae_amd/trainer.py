@@ -6,6 +6,11 @@ the `.step()` / `.save_cpk()` / `.load_cpk(epoch)` surface.  One `train_step` is
 Logger.step iteration (logger.py:150-164): zero_grad -> forward -> loss = sum of weighted
 losses -> backward (gradient all-reduce overlapped) -> Adam.step.  The batch element used
 as the VAE input is `driving`.
+
+With cfg.w_G > 0 or cfg.w_F > 0 the iteration is the reference's whole GAN iteration
+(logger.py:150-172): the generator update adds the hinge GAN and feature-matching terms from a
+patch Discriminator (trainer.py:298-303), then the discriminator is updated with its own Adam
+(trainer.py:330-337).  Single process, eager only.
 """
 from __future__ import annotations
 
@@ -20,8 +25,8 @@ import torch.distributed as dist
 from . import config as _config
 from . import distributed
 from .data import to_device_frames
-from .losses import KLDivergenceLoss, ReconLoss
-from .models import FaceVAE
+from .losses import FeatureMatchingLoss, GANLoss, KLDivergenceLoss, ReconLoss
+from .models import Discriminator, FaceVAE
 from .optim import Adam
 
 
@@ -61,6 +66,24 @@ class FaceVAETrainer:
         self.g_optimizers = {k: Adam(m.parameters(), lr=lr, betas=self.cfg.betas) for k, m in self.g_models.items()}
         self.kl, self.recon = KLDivergenceLoss(), ReconLoss()
         self.weights = {"R": self.cfg.w_R, "K": self.cfg.w_K}
+        # adversarial mode (w_G > 0 or w_F > 0): the patch discriminator on the image alone (K = 0)
+        # and its own Adam (logger.py:61); built after the generator models, as the reference does
+        self.adversarial = self.cfg.w_G > 0 or self.cfg.w_F > 0
+        self.d_models, self.d_optimizers = {}, {}
+        if self.adversarial:
+            if graph:
+                raise ValueError("FaceVAETrainer: the adversarial iteration (w_G > 0 or w_F > 0) is not captured as "
+                                 "a HIP graph; use graph=False")
+            if multi:
+                raise NotImplementedError("FaceVAETrainer: the adversarial iteration under multi-rank data "
+                                          "parallelism (the discriminator's gradient all-reduce) is not built")
+            self.discriminator = Discriminator(True, tuple(self.cfg.disc_down_seq), K=0).cuda()
+            if compute_dtype is not None:
+                self.discriminator.set_compute_dtype(compute_dtype)
+            self.d_models = {"discriminator": self.discriminator}
+            self.d_optimizers = {"discriminator": Adam(self.discriminator.parameters(), lr=lr, betas=self.cfg.betas)}
+            self.gan, self.fm = GANLoss(), FeatureMatchingLoss()
+            self.weights.update(G=self.cfg.w_G, F=self.cfg.w_F)
         self._eps_gen = None
         # graph=True: train_step replays one captured HIP graph per batch shape (graph.StepGraph;
         # under DataParallel the graph segments between the collectives); the batch is copied
@@ -91,7 +114,37 @@ class FaceVAETrainer:
         es.copy_(eps)
         return {k: v.clone() for k, v in sg.replay().items()}
 
+    def _adversarial_step(self, x: torch.Tensor, eps: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """logger.py:150-172: generator update with the GAN and feature-matching terms, then the
+        discriminator update.  Four discriminator forwards (real, fake, real, fake), each with its
+        own power iteration, in the reference's order."""
+        D, w = self.discriminator, self.weights
+        for opt in self.g_optimizers.values():
+            opt.zero_grad(set_to_none=True)
+        y, mu, logstd = self.net(x, eps)
+        with torch.no_grad():                      # the real features are the detached operand
+            _, feat_real = D(x)
+        out_fake, feat_fake = D(y)
+        R, K = self.recon((x, y)), self.kl((mu, logstd))
+        G, F = self.gan(out_fake, True, False), self.fm(feat_fake, feat_real)
+        (w["R"] * R + w["K"] * K + w["G"] * G + w["F"] * F).backward()
+        for opt in self.g_optimizers.values():
+            opt.step()
+        # the discriminator's gradients of the generator pass are dropped unread (logger.py:165-166)
+        for opt in self.d_optimizers.values():
+            opt.zero_grad(set_to_none=True)
+        out_real, _ = D(x)
+        out_fake, _ = D(y.detach())
+        G1, G2 = self.gan(out_fake, False, True), self.gan(out_real, True, True)
+        (G1 + G2).backward()
+        for opt in self.d_optimizers.values():
+            opt.step()
+        return {"R": w["R"] * R.detach(), "K": w["K"] * K.detach(), "G": w["G"] * G.detach(), "F": w["F"] * F.detach(),
+                "G1": G1.detach(), "G2": G2.detach(), "y": y}
+
     def _eager_step(self, x: torch.Tensor, eps: torch.Tensor) -> Dict[str, torch.Tensor]:
+        if self.adversarial:
+            return self._adversarial_step(x, eps)
         for opt in self.g_optimizers.values():
             opt.zero_grad(set_to_none=True)
         y, mu, logstd = self.net(x, eps)
@@ -162,7 +215,9 @@ class FaceVAETrainer:
         if not distributed.is_master() or self.ckp_dir is None:
             return
         ckp = {**{k: m.state_dict() for k, m in self.g_models.items()},
+               **{k: m.state_dict() for k, m in self.d_models.items()},
                **{"optimizer_" + k: o.state_dict() for k, o in self.g_optimizers.items()},
+               **{"optimizer_" + k: o.state_dict() for k, o in self.d_optimizers.items()},
                "epoch": self.epoch}
         torch.save(ckp, os.path.join(self.ckp_dir, "%s-checkpoint.pth.tar" % str(self.epoch).zfill(self.zfill_num)))
 
@@ -171,7 +226,11 @@ class FaceVAETrainer:
         ckp = torch.load(path, map_location="cpu", weights_only=True)
         for k, m in self.g_models.items():
             m.load_state_dict(ckp[k])
+        for k, m in self.d_models.items():
+            m.load_state_dict(ckp[k])
         for k, o in self.g_optimizers.items():
+            o.load_state_dict(ckp["optimizer_" + k])
+        for k, o in self.d_optimizers.items():
             o.load_state_dict(ckp["optimizer_" + k])
         self.epoch = ckp["epoch"] + 1
         self._sg = None            # new optimizer state tensors: the next graph step recaptures

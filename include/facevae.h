@@ -124,6 +124,35 @@ int fv_conv2d_bwd_weight(const fv_conv_desc* d, const void* x, const float* pro_
 int fv_conv2d_wgrad_reduce(const fv_conv_desc* d, const float* slab, const float* bias_slab,
                            float* dw_param, float* db, void* stream);
 
+/* ---- stride-2 3x3 convolution, padding 1 (the patch discriminator's down blocks) ----
+ * The entries take a fv_conv_desc with ksize == 3, upsample == 0, pro_act == 0, no sigmoid and
+ * NHWC output (anything else: FV_E_UNSUPPORTED), dtype FV_F32 or FV_BF16.  (h, w) is the OUTPUT
+ * size; the input is (in_h, in_w) = (2h, 2w), NHWC with channel stride cin -- an odd input size,
+ * or any other in_h / in_w, returns FV_E_UNSUPPORTED.
+ * Weights: wk [rows][Kpad] is the generic forward image (it does not depend on the stride);
+ * wt holds the data gradient's four phase images (input-pixel parities (row, column): 1, 2, 2
+ * or 4 live taps of the 9), so that the transposed conv multiplies no zero taps.  Both are
+ * scaled by 1/sigma[0] when sigma != NULL; either of wk / wt may be NULL. */
+size_t fv_conv2d_s2_wk_elems(const fv_conv_desc* d);
+size_t fv_conv2d_s2_wt_elems(const fv_conv_desc* d);
+int fv_conv2d_s2_weight_prep(const fv_conv_desc* d, const float* w_param, const float* sigma, void* wk, void* wt,
+                             void* stream);
+/* y[n][h][w][ldy] = conv(x, wk, stride 2, padding 1) + bias (bias may be NULL) */
+int fv_conv2d_s2_fwd(const fv_conv_desc* d, int in_h, int in_w, const void* x, const void* wk, const float* bias,
+                     void* y, void* stream);
+/* dx[n][2h][2w][cin] (every padded channel written, the padded ones 0); dy has channel stride
+ * ldy_dy == cout padded to a power of two >= 8, its padding channels finite. */
+int fv_conv2d_s2_bwd_data(const fv_conv_desc* d, int in_h, int in_w, const void* dy, int ldy_dy, const void* wt,
+                          void* dx, void* stream);
+/* weight gradient: per-split fp32 slabs, then the reduce into dw_param [cout][cin_valid][3][3]
+ * and db [cout] (bias_slab / db may be NULL); dy channel stride a multiple of 8 >= cout. */
+size_t fv_conv2d_s2_wgrad_slab_elems(const fv_conv_desc* d);
+size_t fv_conv2d_s2_wgrad_bias_slab_elems(const fv_conv_desc* d);
+int fv_conv2d_s2_bwd_weight(const fv_conv_desc* d, int in_h, int in_w, const void* x, const void* dy, int ldy_dy,
+                            float* slab, float* bias_slab, void* stream);
+int fv_conv2d_s2_wgrad_reduce(const fv_conv_desc* d, const float* slab, const float* bias_slab, float* dw_param,
+                              float* db, void* stream);
+
 /* store-pass reductions of the halo-staged 3x3 kernels (fused into the bf16 store of the
  * output tile; one record per 256-pixel tile and wave, [records][2][cout] fp32):
  *   mode 1 (fv_conv2d_fwd_sr): (sum, sum of squares) of the stored output AFTER the residual
@@ -592,6 +621,37 @@ int fv_comm_destroy(fv_comm_t comm);
 int fv_comm_async_error(fv_comm_t comm, int* result);
 int fv_comm_count(fv_comm_t comm, int* nranks);
 int fv_comm_abort(fv_comm_t comm);
+
+/* ------------------------------------------------- patch discriminator pieces ---- */
+/* Instance norm + LeakyReLU over a dense NHWC tensor [n][h][w][c] (c a power of two in
+ * [8, 512], dtype FV_F32 / FV_BF16): nn.InstanceNorm2d(c, affine=True) followed by
+ * LeakyReLU(slope).  Statistics are per (sample, channel) over the h*w plane: biased variance,
+ * invstd = 1 / sqrt(var + eps); there are no running statistics.  mean / invstd are fp32
+ * [n][c].  All sums are fixed-order (fp32 runs, then fp64): bit-reproducible, and a sample's
+ * results depend on that sample alone.  ws: fv_in_ws_bytes bytes of scratch.
+ *   fwd:        y = leaky(gamma * xhat + beta), xhat = (x - mean) * invstd
+ *   bwd_reduce: with g = dout * leaky'(gamma * xhat + beta): dgamma[c] = sum g * xhat,
+ *               dbeta[c] = sum g (over samples and pixels), k [n][2][c] = the plane means of
+ *               (g, g * xhat)
+ *   bwd_apply:  dx = gamma * invstd * (g - k0 - xhat * k1) */
+size_t fv_in_ws_bytes(int n, int h, int w, int c);
+int fv_in_stats(int dtype, const void* x, int n, int h, int w, int c, float eps, float* mean, float* invstd, void* ws,
+                void* stream);
+int fv_in_act_fwd(int dtype, const void* x, int n, int h, int w, int c, const float* mean, const float* invstd,
+                  const float* gamma, const float* beta, float slope, void* y, void* stream);
+int fv_in_act_bwd_reduce(int dtype, const void* dout, const void* x, int n, int h, int w, int c, const float* mean,
+                         const float* invstd, const float* gamma, const float* beta, float slope, float* dgamma,
+                         float* dbeta, float* k, void* ws, void* stream);
+int fv_in_act_bwd_apply(int dtype, const void* dout, const void* x, int n, int h, int w, int c, const float* mean,
+                        const float* invstd, const float* gamma, const float* beta, float slope, const float* k,
+                        void* dx, void* stream);
+/* Discriminator input: out NHWC [n][h][w][ldc] of `dtype` (ldc a power of two in [8, 32],
+ * >= 3 + k) from the NCHW fp32 image [n][3][h][w] and the keypoints kp [n][k][kp_stride]
+ * (kp_stride >= 2; kp may be NULL when k == 0).  Channels 0-2: the image; channel 3 + j:
+ * exp(-0.5 ((gx - kp[j][0])^2 + (gy - kp[j][1])^2) / 0.01) with gx = 2 w / (W - 1) - 1,
+ * gy = 2 h / (H - 1) - 1; the padding channels 0.  h, w >= 2. */
+int fv_disc_input_fwd(int dtype, const float* img, const float* kp, int n, int h, int w, int k, int kp_stride, int ldc,
+                      void* out, void* stream);
 
 #ifdef __cplusplus
 }
