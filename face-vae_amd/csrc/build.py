@@ -19,8 +19,10 @@ PKG = os.path.dirname(HERE)
 ROOT = os.path.dirname(PKG)
 OUT = os.path.join(PKG, "libfacevae.so")
 BUILD = os.path.join(HERE, "build")
-SOURCES = ["abi.cpp", "conv.hip", "conv3d.hip", "warp.hip", "vgg.hip", "convt.hip", "bn.hip", "disc.hip", "misc.hip", "comm.cpp"]
-HEADERS = ["common.h", os.path.join(ROOT, "include", "facevae.h")]
+# the 2-D convolution is several files sharing conv_common.h; the longest compiles first
+SOURCES = ["conv.hip", "conv_fwd_v2.hip", "conv_fwd.hip", "abi.cpp", "conv3d.hip", "warp.hip", "vgg.hip", "convt.hip",
+           "bn.hip", "disc.hip", "misc.hip", "comm.cpp"]
+HEADERS = ["common.h", "conv_common.h", os.path.join(ROOT, "include", "facevae.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-mcode-object-version=5", "-I" + os.path.join(ROOT, "include")]
@@ -52,7 +54,7 @@ def build(jobs=None, force=False, verbose=True, diag=False):
     out = os.path.join(build_dir, "libfacevae_diag.so") if diag else OUT
     extra = ["-DFV_DIAG"] if diag else []
     os.makedirs(build_dir, exist_ok=True)
-    jobs = jobs or min(len(SOURCES), os.cpu_count() or 1)
+    jobs = jobs or min(len(SOURCES), 16, os.cpu_count() or 1)
     with ThreadPoolExecutor(jobs) as ex:
         res = list(ex.map(lambda s: _compile(s, force, build_dir, extra), SOURCES))
     errs = [e for _, e in res if e]

@@ -1,15 +1,21 @@
 #!/bin/bash
-# A/B helper: build libfacevae.so from a committed source (default conv.hip at HEAD) into
-# abl/libfacevae_<tag>.so, linking this tree's other objects (run after face-vae_amd/csrc/build.py).
-#   bash tools/build_head_lib.sh [rev] [tag] [file]      e.g.  bash tools/build_head_lib.sh HEAD head bn.hip
-set -e
-REV=${1:-HEAD}; TAG=${2:-head}; SRC=${3:-conv.hip}
+# A/B helper: build libfacevae.so from the committed sources of a revision (default HEAD) into
+# abl/libfacevae_<tag>.so.  The revision's face-vae_amd/csrc and include are checked out into a
+# temporary directory and built there with that revision's own build.py (so python must be on
+# PATH, as for every build of the library); the working tree and its objects are not touched.
+# Select the result with FV_LIB_PATH.
+#   bash tools/build_head_lib.sh [rev] [tag]      e.g.  bash tools/build_head_lib.sh HEAD~1 parent
+# (The former third argument, one source file to rebuild at the revision and link against this
+# tree's other objects, is gone: the convolution's files share internal declarations, so only a
+# whole revision builds.)
+set -e -o pipefail
+REV=${1:-HEAD}; TAG=${2:-head}
+[ $# -le 2 ] || { echo "usage: $0 [rev] [tag]" >&2; exit 2; }
 cd "$(dirname "$0")/.."
-git show "$REV":face-vae_amd/csrc/$SRC > face-vae_amd/csrc/ab_tmp_$SRC
-(cd face-vae_amd/csrc && /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -w -mcode-object-version=5 \
-   -I../../include -x hip -c ab_tmp_$SRC -o /tmp/ab_tmp.o) || { rm -f face-vae_amd/csrc/ab_tmp_$SRC; exit 1; }
-rm -f face-vae_amd/csrc/ab_tmp_$SRC
+TMP=$(mktemp -d)
+trap 'rm -rf "$TMP"' EXIT
+git archive "$REV" face-vae_amd/csrc include | tar -x -C "$TMP"
+python "$TMP/face-vae_amd/csrc/build.py" --force
 mkdir -p abl
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o abl/libfacevae_$TAG.so /tmp/ab_tmp.o \
-  $(ls face-vae_amd/csrc/build/*.o | grep -v "/$SRC.o") -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
-echo "built abl/libfacevae_$TAG.so from $REV:$SRC"
+cp "$TMP/face-vae_amd/libfacevae.so" "abl/libfacevae_$TAG.so"
+echo "built abl/libfacevae_$TAG.so from $REV"
