@@ -10,16 +10,17 @@ through the C-ABI in include/facevae.h.
 from . import _lib
 from .config import FaceVAEConfig, compute_dtype, set_compute_dtype
 from .losses import FeatureMatchingLoss, GANLoss, KLDivergenceLoss, L1Loss, PerceptualLoss, ReconLoss
-from .models import AFE, Discriminator, FaceVAE, Generator
-from .modules import (Conv2d, ConvBlock2D, ConvBlock3D, ConvTranspose2dELR, DownBlock2D, ResBlock2D, ResBlock3D,
-                      SameBlock2D, UpBlock2D)
+from .models import AFE, MFE, Discriminator, FaceVAE, Generator
+from .modules import (Conv2d, Conv3d, ConvBlock2D, ConvBlock3D, ConvTranspose2dELR, DownBlock2D, DownBlock3D,
+                      ResBlock2D, ResBlock3D, SameBlock2D, UpBlock2D, UpBlock3D)
 from .optim import Adam
 from . import checkpoint, distributed, graph, ops, ops3d, warp
 from .graph import StepGraph
 
 __all__ = ["FaceVAEConfig", "compute_dtype", "set_compute_dtype", "KLDivergenceLoss", "L1Loss", "PerceptualLoss", "ReconLoss",
            "AFE", "FaceVAE", "Generator", "Conv2d", "ConvBlock2D", "ConvTranspose2dELR", "DownBlock2D", "ResBlock2D", "ResBlock3D", "ConvBlock3D", "SameBlock2D",
-           "UpBlock2D", "Adam", "distributed", "ops", "FaceVAETrainer", "Discriminator", "GANLoss", "FeatureMatchingLoss"]
+           "UpBlock2D", "Adam", "distributed", "ops", "FaceVAETrainer", "Discriminator", "GANLoss", "FeatureMatchingLoss",
+           "MFE", "DownBlock3D", "UpBlock3D", "Conv3d"]
 
 
 def __getattr__(name):

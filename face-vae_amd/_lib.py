@@ -35,6 +35,11 @@ class Conv3dDesc(ctypes.Structure):
                 ("cin", c_int), ("cout", c_int)]
 
 
+class Conv3dgDesc(ctypes.Structure):
+    _fields_ = [("dtype", c_int), ("n", c_int), ("d", c_int), ("h", c_int), ("w", c_int),
+                ("cin", c_int), ("cout", c_int), ("ksize", c_int), ("upsample", c_int)]
+
+
 class StoreReduce(ctypes.Structure):
     _fields_ = [("mode", c_int), ("records", c_void_p), ("bn_input", c_void_p), ("mean", c_void_p),
                 ("invstd", c_void_p), ("gamma", c_void_p), ("beta", c_void_p), ("slope", c_float)]
@@ -53,6 +58,7 @@ class AdamTensor(ctypes.Structure):
 P = c_void_p
 D = POINTER(ConvDesc)
 D3 = POINTER(Conv3dDesc)
+D3G = POINTER(Conv3dgDesc)
 # name -> (restype, argtypes)
 _SIGS = {
     "fv_abi_version": (c_int, []),
@@ -121,6 +127,15 @@ _SIGS = {
     "fv_conv3d_bwd_data": (c_int, [D3, P, P, P, P]),
     "fv_conv3d_wgrad_ws_bytes": (c_size_t, [D3]),
     "fv_conv3d_bwd_weight": (c_int, [D3, P, P, P, P, P, P]),
+    "fv_conv3dg_check": (c_int, [D3G]),
+    "fv_conv3dg_wk_bytes": (c_size_t, [D3G]),
+    "fv_conv3dg_wt_bytes": (c_size_t, [D3G]),
+    "fv_conv3dg_weight_prep": (c_int, [D3G, P, P, P, P]),
+    "fv_conv3dg_fwd": (c_int, [D3G, P, P, P, P, P]),
+    "fv_conv3dg_bwd_data": (c_int, [D3G, P, P, P, P]),
+    "fv_conv3dg_upsample_bwd": (c_int, [D3G, P, P, P]),
+    "fv_conv3dg_wgrad_ws_bytes": (c_size_t, [D3G]),
+    "fv_conv3dg_bwd_weight": (c_int, [D3G, P, P, P, P, P, P]),
     "fv_depth_split": (c_int, [c_int, P, c_int, c_int, c_int, c_int, c_int, P, P]),
     "fv_grid_sample3d_fwd": (c_int, [c_int, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                      P, P]),

@@ -9,7 +9,8 @@ from torch import nn
 from . import config as _config
 from . import ops
 from . import ops3d, warp
-from .modules import Conv2d, ConvBlock2D, DownBlock2D, ResBlock2D, ResBlock3D, UpBlock2D, _Block
+from .modules import (Conv2d, Conv3d, ConvBlock2D, DownBlock2D, DownBlock3D, ResBlock2D, ResBlock3D, UpBlock2D,
+                      UpBlock3D, _Block)
 
 
 def _batched_weight_prep(model, device):
@@ -63,6 +64,56 @@ class AFE(_Block):
             N, C, D, H, W = fs.shape
             wb.prep(ops3d.desc3(ops.storage(self.compute_dtype()), N, D, H, W, C, C), x.device)
         return self.res(fs)
+
+
+class MFE(_Block):
+    """Motion field estimator (models.py:1040-1082): 1x1x1 `compress` of the appearance volume,
+    the keypoint heatmaps and the K+1 sparse motions with the compressed volume sampled at each
+    (warp.py), a 3-D hourglass (DownBlock3D / UpBlock3D chains), then the 7x7x7 `mask_conv` whose
+    softmax blends the sparse motions into the dense deformation, and the 7x7 `occlusion_conv`
+    over the depth-merged features.  forward(fs, kp_s, kp_d, Rs, Rd) -> (deformation
+    [N, D, H, W, 3], occlusion [N, 1, H, W], mask [N, K+1, D, H, W, 1]), all fp32.
+
+    Every conv runs on the HIP kernels (3-D: ops3d.CNA3DFn / Conv3dFn on conv3d_gemm.hip; the
+    occlusion conv on the 2-D path with its fused sigmoid).  The two concatenations
+    (models.py:1071, 1074) are torch copies of NDHWC tensors."""
+
+    def __init__(self, use_weight_norm=False, down_seq=(80, 64, 128, 256, 512, 1024),
+                 up_seq=(1024, 512, 256, 128, 64, 32), K=15, D=16, C1=32, C2=4):
+        super().__init__()
+        if use_weight_norm:
+            raise NotImplementedError("facevae_amd MFE: use_weight_norm=False only (no spectral norm on 3-D convs)")
+        down_seq, up_seq = list(down_seq), list(up_seq)
+        self.compress = Conv3d(C1, C2, 1, 1, 0)
+        self.down = nn.Sequential(*[DownBlock3D(down_seq[i], down_seq[i + 1], use_weight_norm)
+                                    for i in range(len(down_seq) - 1)])
+        self.up = nn.Sequential(*[UpBlock3D(up_seq[i], up_seq[i + 1], use_weight_norm)
+                                  for i in range(len(up_seq) - 1)])
+        self.mask_conv = Conv3d(down_seq[0] + up_seq[-1], K + 1, 7, 1, 3)
+        self.occlusion_conv = Conv2d((down_seq[0] + up_seq[-1]) * D, 1, 7, 1, 3)
+        self.C, self.D = down_seq[0] + up_seq[-1], D
+
+    def forward(self, fs, kp_s, kp_d, Rs, Rd):
+        if not fs.is_cuda:
+            raise RuntimeError("facevae_amd ops run on the GPU only (HIP); got a CPU tensor")
+        mode = self.compute_dtype()
+        dtype = ops.storage(mode)
+        _batched_weight_prep(self, fs.device)
+        N, _, D, H, W = fs.shape
+        fc = self.compress(fs)                                               # [N, C2, D, H, W]
+        heat = warp.create_heatmap_representations(fc, kp_s, kp_d)           # [N, K+1, 1, D, H, W]
+        sparse_motion = warp.create_sparse_motions(fc, kp_s, kp_d, Rs, Rd)   # [N, K+1, D, H, W, 3]
+        deformed = warp.create_deformed_source_image(fc, sparse_motion, dtype)   # [N, K+1, C2, D, H, W]
+        # cat(dim=2).view(N, -1, D, H, W) (models.py:1071): channel = k * (C2 + 1) + c, built
+        # directly in NDHWC order [N, D, H, W, K+1, C2+1]
+        inp = torch.cat([heat.to(dtype).permute(0, 3, 4, 5, 1, 2), deformed.permute(0, 3, 4, 5, 1, 2)], dim=5)
+        inp = inp.reshape(N, D, H, W, -1).permute(0, 4, 1, 2, 3)
+        out = self.up(self.down(inp))
+        x = torch.cat([inp, out], dim=1).contiguous(memory_format=ops3d.CL3)   # models.py:1074
+        mask_logits = self.mask_conv(x)
+        deformation, mask = warp.deformation_from_mask(mask_logits, sparse_motion)
+        occlusion = self.occlusion_conv(ops3d.depth_merge(x, mode), sigmoid=True)   # models.py:1080-1081
+        return deformation, occlusion, mask
 
 
 class Generator(_Block):

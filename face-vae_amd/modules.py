@@ -306,27 +306,86 @@ class _Conv3(nn.Module):
 
 class ConvBlock3D(_Block):
     """_ConvBlock with dim=3 (modules.py:52-56): parameter / buffer holder with the reference
-    state-dict keys.  It runs inside ResBlock3D ("NAC", 3x3x3, stride 1, padding 1); spectral
+    state-dict keys.  "NAC" (3x3x3, stride 1, padding 1) runs inside ResBlock3D; "CNA" (kernel 3
+    or 1, stride 1, padding kernel // 2: DownBlock3D / UpBlock3D / SameBlock3D, modules.py:59-113)
+    runs on the general 3-D conv kernels (ops3d.CNA3DFn).  SyncBatchNorm + ReLU only; spectral
     norm and the other patterns raise."""
 
     def __init__(self, pattern, in_channels, out_channels, kernel_size, stride, padding, use_weight_norm,
                  activation_type="batch", nonlinearity_type="relu"):
         super().__init__()
-        if (kernel_size, stride, padding) != (3, 1, 1) or pattern != "NAC" or use_weight_norm:
-            raise NotImplementedError("facevae_amd ConvBlock3D: the ResBlock3D form only (NAC, 3x3x3, s1, p1, "
-                                      "no spectral norm: AFE uses use_weight_norm=False, models.py:930)")
+        if use_weight_norm:
+            raise NotImplementedError("facevae_amd ConvBlock3D: no spectral norm (AFE and MFE use "
+                                      "use_weight_norm=False, models.py:930, 1052)")
+        if pattern not in ("NAC", "CNA"):
+            raise NotImplementedError(f"facevae_amd ConvBlock3D: pattern {pattern!r} (supported: 'NAC', 'CNA')")
+        kernels = (3,) if pattern == "NAC" else (1, 3)
+        if kernel_size not in kernels or stride != 1 or padding != kernel_size // 2:
+            raise NotImplementedError(f"facevae_amd ConvBlock3D {pattern}: kernel size in {kernels}, stride 1, "
+                                      "padding kernel_size // 2")
         if activation_type != "batch" or nonlinearity_type != "relu":
             raise NotImplementedError("facevae_amd ConvBlock3D: SyncBatchNorm + ReLU only")
         self.pattern = pattern
+        norm_channels = out_channels if pattern == "CNA" else in_channels
         mappings = {"C": _Conv3(in_channels, out_channels, kernel_size),
-                    "N": _BatchNorm(in_channels),
+                    "N": _BatchNorm(norm_channels),
                     "A": _Act(nonlinearity_type)}
         self.layers = nn.Sequential(*[mappings[c] for c in pattern])
         _ref(self, "conv", mappings["C"])
         _ref(self, "bn", mappings["N"])
+        self.upsample = False
+        self.pool = False
 
     def forward(self, x):
-        raise NotImplementedError("ConvBlock3D runs inside ResBlock3D (ops3d.ResBlock3DFn)")
+        if self.pattern != "CNA":
+            raise NotImplementedError("ConvBlock3D 'NAC' runs inside ResBlock3D (ops3d.ResBlock3DFn)")
+        from . import ops3d
+        return ops3d.CNA3DFn.apply(x, self.conv.weight, self.conv.bias, self.bn.weight, self.bn.bias, self)
+
+
+class DownBlock3D(_Block):
+    """CNA 3x3x3 then AvgPool3d((1, 2, 2)) (modules.py:59-75); pool fused into the BN/act pass."""
+
+    def __init__(self, in_channels, out_channels, use_weight_norm):
+        super().__init__()
+        cb = ConvBlock3D("CNA", in_channels, out_channels, 3, 1, 1, use_weight_norm)
+        cb.pool = True
+        self.layers = nn.Sequential(cb, _AvgPool())
+
+    def forward(self, x):
+        return self.layers[0](x)
+
+
+class UpBlock3D(_Block):
+    """Upsample((1, 2, 2), nearest) then CNA 3x3x3 (modules.py:78-94); the upsample is folded
+    into the conv's input addressing, never materialised."""
+
+    def __init__(self, in_channels, out_channels, use_weight_norm):
+        super().__init__()
+        cb = ConvBlock3D("CNA", in_channels, out_channels, 3, 1, 1, use_weight_norm)
+        cb.upsample = True
+        self.layers = nn.Sequential(_Upsample(), cb)
+
+    def forward(self, x):
+        return self.layers[1](x)
+
+
+class Conv3d(_Conv3):
+    """nn.Conv3d drop-in (stride 1, 'same' padding, kernel 1 / 3 / 7) with state-dict keys weight /
+    bias, on the general 3-D conv kernels (ops3d.Conv3dFn); output NDHWC in the storage dtype."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, bias=True):
+        if stride != 1 or padding != kernel_size // 2 or kernel_size not in (1, 3, 7):
+            raise NotImplementedError("facevae_amd Conv3d: kernel 1, 3 or 7, stride 1, 'same' padding only")
+        super().__init__(in_channels, out_channels, kernel_size, bias)
+        self._dtype = None
+
+    def compute_dtype(self):
+        return self._dtype or config.compute_dtype()
+
+    def forward(self, x):
+        from . import ops3d
+        return ops3d.Conv3dFn.apply(x, self.weight, self.bias, self.kernel_size, ops.storage(self.compute_dtype()))
 
 
 class ResBlock3D(_Block):

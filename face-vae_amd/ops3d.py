@@ -238,7 +238,9 @@ class DepthMergeFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         N, C, D, H, W = ctx.shape
-        gb, _ = ops.to_nhwc(g, ctx.dtype)
+        # dense NHWC with exactly C*D channels (to_nhwc would pad a channel count that is no
+        # power of two, e.g. the MFE's 112 * 16, which this permutation must not see)
+        gb = ops.grad_in(g, ctx.dtype)
         dfs = torch.empty((N, C, D, H, W), dtype=ctx.dtype, device=g.device, memory_format=CL3)
         call("fv_depth_split", L.dtype_code(ctx.dtype), ptr(gb), N, H * W, C, D, 0, ptr(dfs), stream())
         return dfs.to(ctx.fdtype), None
@@ -250,3 +252,175 @@ def depth_split(h, C, D, mode):
 
 def depth_merge(fs, mode):
     return DepthMergeFn.apply(fs, ops.storage(mode))
+
+
+# ----------------------------------------------------------------------------------------
+# general-channel 3-D convs of the MFE (conv3d_gemm.hip, fv_conv3dg_*)
+# ----------------------------------------------------------------------------------------
+
+def descg(dtype, n, d, h, w, cin, cout, ksize, ups=False):
+    """Descriptor of a general 3-D conv; (d, h, w) is the OUTPUT volume (twice the input's h, w
+    under `ups`)."""
+    return L.Conv3dgDesc(L.dtype_code(dtype), n, d, h, w, cin, cout, ksize, int(bool(ups)))
+
+
+class Conv3dgState:
+    """Per-forward prepared weights of one general Conv3d: wk (forward) and wt (data gradient)."""
+
+    def __init__(self, w, d, device, need_wt):
+        if w.dtype != F32 or not w.is_contiguous():
+            raise RuntimeError("conv3d weights must be contiguous fp32")
+        call("fv_conv3dg_check", ctypes.byref(d))          # raises FaceVAELibError when unsupported
+        self.d, self.w = d, w
+        self.wk = torch.empty(query("fv_conv3dg_wk_bytes", ctypes.byref(d)), dtype=torch.uint8, device=device)
+        self.wt = None
+        if need_wt:
+            self.wt = torch.empty(query("fv_conv3dg_wt_bytes", ctypes.byref(d)), dtype=torch.uint8, device=device)
+        call("fv_conv3dg_weight_prep", ctypes.byref(d), ptr(w), ptr(self.wk), ptr(self.wt), stream())
+
+    def release(self):
+        self.wk = None
+
+
+def _tdtype(d):
+    return torch.bfloat16 if d.dtype == L.FV_BF16 else F32
+
+
+def conv3dg_forward(cs: Conv3dgState, x, bias):
+    """x NDHWC [n, cin, d, h(/2), w(/2)] -> y NDHWC [n, cout, d, h, w]."""
+    d = cs.d
+    hin, win = (d.h // 2, d.w // 2) if d.upsample else (d.h, d.w)
+    if tuple(x.shape) != (d.n, d.cin, d.d, hin, win) or x.dtype != _tdtype(d) or not x.is_contiguous(memory_format=CL3):
+        raise RuntimeError(f"conv3dg: input {tuple(x.shape)} {x.dtype} does not match its descriptor")
+    y = torch.empty((d.n, d.cout, d.d, d.h, d.w), dtype=x.dtype, device=x.device, memory_format=CL3)
+    call("fv_conv3dg_fwd", ctypes.byref(d), ptr(x), ptr(cs.wk), ptr(bias), ptr(y), stream())
+    return y
+
+
+def conv3dg_backward(cs: Conv3dgState, x, dy, need_dx=True, need_db=True):
+    """-> (dx NDHWC like x or None, dw fp32 in the parameter layout, db fp32 or None)."""
+    d = cs.d
+    dev = dy.device
+    if tuple(dy.shape) != (d.n, d.cout, d.d, d.h, d.w) or dy.dtype != x.dtype or not dy.is_contiguous(memory_format=CL3):
+        raise RuntimeError(f"conv3dg: gradient {tuple(dy.shape)} {dy.dtype} does not match its descriptor")
+    dw = torch.empty_like(cs.w)
+    db = torch.empty(d.cout, dtype=F32, device=dev) if need_db else None
+    ws = ops._empty(query("fv_conv3dg_wgrad_ws_bytes", ctypes.byref(d)), torch.uint8, dev)
+    call("fv_conv3dg_bwd_weight", ctypes.byref(d), ptr(x), ptr(dy), ptr(dw), ptr(db), ptr(ws), stream())
+    dx = None
+    if need_dx:
+        dx = torch.empty((d.n, d.cin, d.d, d.h, d.w), dtype=dy.dtype, device=dev, memory_format=CL3)
+        call("fv_conv3dg_bwd_data", ctypes.byref(d), ptr(dy), ptr(cs.wt), ptr(dx), stream())
+        if d.upsample:
+            lo = torch.empty((d.n, d.cin, d.d, d.h // 2, d.w // 2), dtype=dy.dtype, device=dev, memory_format=CL3)
+            call("fv_conv3dg_upsample_bwd", ctypes.byref(d), ptr(dx), ptr(lo), stream())
+            dx = lo
+    return dx, dw, db
+
+
+class Conv3dFn(torch.autograd.Function):
+    """Bare nn.Conv3d(cin, cout, k, 1, k // 2) with bias (MFE.compress, MFE.mask_conv:
+    models.py:1054, 1057): y NDHWC in the storage dtype."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, ksize, dtype):
+        xb = to_ndhwc(x, dtype)
+        N, C, D, H, W = xb.shape
+        d = descg(dtype, N, D, H, W, C, weight.shape[0], ksize)
+        cs = Conv3dgState(weight, d, x.device, ctx.needs_input_grad[0])
+        y = conv3dg_forward(cs, xb, bias)
+        cs.release()
+        ctx.cs = cs
+        ctx.save_for_backward(x, xb)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, xb = ctx.saved_tensors
+        dx, dw, db = conv3dg_backward(ctx.cs, xb, to_ndhwc(dy, xb.dtype), ctx.needs_input_grad[0],
+                                      ctx.needs_input_grad[2])
+        if dx is not None and dx.dtype != x.dtype:
+            dx = dx.to(x.dtype)
+        return dx, dw, db, None, None
+
+
+class _PaddedBN:
+    """BN holder padded to `cp` channels (gamma 1, beta 0, mean 0, var 1 in the pad) for the BN
+    kernels, which take 8 * 2^k channels; the padded conv channels are all zero, stay zero
+    through BN + ReLU, and are cut off again.  Only channel counts that are not 8 * 2^k (none
+    in the default MFE) come this way."""
+
+    def __init__(self, bn, gamma, beta, cp):
+        c = bn.num_features
+        dev = gamma.device
+        one, zero = torch.ones(cp - c, device=dev), torch.zeros(cp - c, device=dev)
+        self.bn, self.num_features, self.eps, self.momentum = bn, cp, bn.eps, bn.momentum
+        self.track_running_stats = bn.track_running_stats
+        self.weight = torch.cat([gamma.detach(), one])
+        self.bias = torch.cat([beta.detach(), zero])
+        self.running_mean = torch.cat([bn.running_mean, zero])
+        self.running_var = torch.cat([bn.running_var, one])
+        self.num_batches_tracked = bn.num_batches_tracked
+
+    def write_back(self):
+        c = self.bn.num_features
+        self.bn.running_mean.copy_(self.running_mean[:c])
+        self.bn.running_var.copy_(self.running_var[:c])
+
+
+def _pad_rows(t, cp):
+    return torch.cat([t.detach(), t.new_zeros((cp - t.shape[0],) + tuple(t.shape[1:]))]).contiguous()
+
+
+class CNA3DFn(torch.autograd.Function):
+    """ConvBlock3D "CNA": Conv3d -> SyncBatchNorm -> ReLU (modules.py:8-42, 52-56), with
+    DownBlock3D's AvgPool3d((1, 2, 2)) fused into the BN/ReLU pass (blk.pool) or UpBlock3D's
+    nearest (1, 2, 2) upsample folded into the conv's gather (blk.upsample) (modules.py:59-94).
+    In NDHWC the [N, C, D*H, W] alias turns both into their 2-D 2x2 forms (row d*H + h <-> rows
+    2(d*H + h), +1 as H is even), so the BN kernels of ops.py run unchanged."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, gamma, beta, blk):
+        dtype = ops.storage(blk.compute_dtype())
+        xb = to_ndhwc(x, dtype)
+        N, Cin, D, Hi, Wi = xb.shape
+        H, W = (2 * Hi, 2 * Wi) if blk.upsample else (Hi, Wi)
+        conv, bn = blk.conv, blk.bn
+        cout = conv.out_channels
+        cp = ops.pad_pow2(cout)
+        training = blk.training
+        comm = blk.bn_comm()
+        pbn = bn
+        if cp != cout:
+            weight, bias, pbn = _pad_rows(weight, cp), _pad_rows(bias, cp), _PaddedBN(bn, gamma, beta, cp)
+        d = descg(dtype, N, D, H, W, Cin, cp, conv.kernel_size, blk.upsample)
+        cs = Conv3dgState(weight, d, x.device, ctx.needs_input_grad[0])
+        y = conv3dg_forward(cs, xb, bias)
+        r = ops.bn_from_tensor(pbn, as4d(y), training, comm)
+        if training and pbn is not bn:
+            pbn.write_back()
+        z = as5d(ops.bn_act_forward(as4d(y), r, 0.0, blk.pool, pbn), D)
+        if cp != cout:
+            z = z[:, :cout].contiguous(memory_format=CL3)
+        cs.release()
+        ctx.blk, ctx.cs, ctx.r, ctx.comm, ctx.pbn, ctx.cout = blk, cs, r, comm, pbn, cout
+        ctx.save_for_backward(x, xb, y)
+        return z
+
+    @staticmethod
+    def backward(ctx, dz):
+        x, xb, y = ctx.saved_tensors
+        blk, cs, r, cout = ctx.blk, ctx.cs, ctx.r, ctx.cout
+        D = y.shape[2]
+        cp = y.shape[1]
+        dz = to_ndhwc(dz, y.dtype)
+        if cp != cout:
+            full = torch.zeros((dz.shape[0], cp) + tuple(dz.shape[2:]), dtype=dz.dtype, device=dz.device).contiguous(
+                memory_format=CL3)
+            full[:, :cout] = dz
+            dz = full
+        dy, dg, dbt = ops.bn_act_backward(as4d(dz), as4d(y), ctx.pbn, r, 0.0, blk.pool, ctx.comm)
+        dx, dw, db = conv3dg_backward(cs, xb, as5d(dy, D), ctx.needs_input_grad[0])
+        if dx is not None and dx.dtype != x.dtype:
+            dx = dx.to(x.dtype)
+        return dx, dw[:cout], db[:cout], dg[:cout], dbt[:cout], None

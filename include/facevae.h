@@ -27,6 +27,8 @@
  *   fv_mse_*                 ReconLoss / nn.MSELoss (losses.py:396-403).
  *   fv_l1_*                  PerceptualLoss pixel term nn.L1Loss (losses.py:128,135).
  *   fv_conv3d_*             nn.Conv3d of ResBlock3D (modules.py:52-56,133-135; AFE models.py:935).
+ *   fv_conv3dg_*            nn.Conv3d of DownBlock3D / UpBlock3D (modules.py:59-94) and of the MFE's
+ *                           compress / mask_conv (models.py:1054, 1057): general-channel implicit GEMM.
  *   fv_grid_sample3d_*, fv_occlusion_*, fv_sparse_motion_*, fv_heatmap_*, fv_motion_mask_*
  *                            warp path: models.py:1076-1078,1103,1106; utils.py:123-179.
  *   fv_adam_step             torch.optim.Adam(lr, betas=(0.5,0.999)) (logger.py:60-61).
@@ -347,6 +349,45 @@ int fv_conv3d_bwd_weight(const fv_conv3d_desc* d, const void* x, const void* dy,
  * (inverse = 1: src NDHWC, dst NHWC) */
 int fv_depth_split(int dtype, const void* src, int n, int hw, int c, int d_count, int inverse, void* dst,
                    void* stream);
+
+/* ------------------------------- general 3-D conv (MFE hourglass, compress, mask) ---- */
+/* nn.Conv3d(cin, cout, k, 1, k / 2), k = 1 / 3 / 7, of the MFE (models.py:1054-1057, 1063, 1072-1075):
+ * the "CNA" ConvBlock3D of DownBlock3D / UpBlock3D (modules.py:59-94), the 1x1x1 compress and the
+ * 7x7x7 mask conv.  An implicit GEMM on the matrix units for both dtypes (bf16: 16x16x32 bf16
+ * MFMA; fp32: the exact 16x16x4 f32 MFMA), fp32 accumulation.  Activations NDHWC, dense; weights
+ * in the reference layout [cout][cin][k][k][k] fp32, re-laid out per forward by
+ * fv_conv3dg_weight_prep.  cin must be a positive multiple of 8; cout, d, h, w are free.
+ * upsample = 1 folds UpBlock3D's nn.Upsample(scale_factor=(1, 2, 2)) (modules.py:81, 94) into the
+ * gather: x is then [n][d][h / 2][w / 2][cin] and is read at (d, h >> 1, w >> 1).
+ * Unsupported descriptors (cin % 8 != 0, another ksize, upsample with odd h or w) return
+ * FV_E_UNSUPPORTED from every entry (the byte queries return 0). */
+typedef struct fv_conv3dg_desc {
+  int dtype;         /* FV_F32 or FV_BF16 */
+  int n, d, h, w;    /* OUTPUT volume */
+  int cin, cout;     /* channels (dense, channel stride == count) */
+  int ksize;         /* 1, 3 or 7 (cubic), stride 1, padding ksize / 2 */
+  int upsample;      /* 1: nearest (1, 2, 2) upsample of x in front of the conv */
+} fv_conv3dg_desc;
+int fv_conv3dg_check(const fv_conv3dg_desc* d);
+/* bytes of the forward (wk) and data-gradient (wt: transposed, taps flipped) weight layouts */
+size_t fv_conv3dg_wk_bytes(const fv_conv3dg_desc* d);
+size_t fv_conv3dg_wt_bytes(const fv_conv3dg_desc* d);
+int fv_conv3dg_weight_prep(const fv_conv3dg_desc* d, const float* w_param, void* wk, void* wt, void* stream);
+/* y [n][d][h][w][cout] = conv3d(x, wk) + bias (bias may be NULL) */
+int fv_conv3dg_fwd(const fv_conv3dg_desc* d, const void* x, const void* wk, const float* bias, void* y,
+                   void* stream);
+/* dx [n][d][h][w][cin] at the OUTPUT resolution from dy [n][d][h][w][cout] and wt; with upsample
+ * the caller then sums the 2x2 phases (fv_upsample2x_bwd on the [n][d * h][w][cin] alias) */
+int fv_conv3dg_bwd_data(const fv_conv3dg_desc* d, const void* dy, const void* wt, void* dx, void* stream);
+/* backward of the folded upsample for ANY cin % 8 == 0: out [n][d][h / 2][w / 2][cin] = the 2x2
+ * phase sums of g [n][d][h][w][cin] (fv_upsample2x_bwd takes 8 * 2^k channels only) */
+int fv_conv3dg_upsample_bwd(const fv_conv3dg_desc* d, const void* g, void* out, void* stream);
+/* dw[cout][cin][k][k][k] fp32 and db [cout] (may be NULL) from x (the conv's input, low
+ * resolution under upsample) and dy: voxel-split fp32 slabs summed in a fixed order, no float
+ * atomics (bit-reproducible); ws of fv_conv3dg_wgrad_ws_bytes bytes */
+size_t fv_conv3dg_wgrad_ws_bytes(const fv_conv3dg_desc* d);
+int fv_conv3dg_bwd_weight(const fv_conv3dg_desc* d, const void* x, const void* dy, float* dw, float* db, void* ws,
+                          void* stream);
 
 /* ------------------------------------------------------- warp path (Generator / MFE) ---- */
 /* F.grid_sample(in, grid, mode="bilinear" (trilinear), padding_mode="zeros",
