@@ -237,6 +237,23 @@ _SIGS = {
     "fv_in_act_bwd_reduce": (c_int, [c_int, P, P, c_int, c_int, c_int, c_int, P, P, P, P, c_float, P, P, P, P, P]),
     "fv_in_act_bwd_apply": (c_int, [c_int, P, P, c_int, c_int, c_int, c_int, P, P, P, P, c_float, P, P, P]),
     "fv_disc_input_fwd": (c_int, [c_int, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
+    "fv_stem7s2_wk_elems": (c_size_t, [c_int]),
+    "fv_stem7s2_weight_prep": (c_int, [c_int, P, c_int, P, P]),
+    "fv_stem7s2_stats_blocks": (c_int, [c_int, c_int, c_int]),
+    "fv_stem7s2_stats_block_pixels": (c_int, []),
+    "fv_stem7s2_fwd": (c_int, [c_int, P, c_int, c_int, c_int, c_int, P, P, P, P, P]),
+    "fv_stem7s2_wgrad_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "fv_stem7s2_bwd_weight": (c_int, [c_int, P, P, c_int, c_int, c_int, c_int, P, P, P, P]),
+    "fv_maxpool3s2_fwd": (c_int, [c_int, P, c_int, c_int, c_int, c_int, P, P, c_float, P, P, P]),
+    "fv_maxpool3s2_bwd": (c_int, [c_int, P, P, c_int, c_int, c_int, c_int, P, P]),
+    "fv_subsample2_fwd": (c_int, [c_int, P, c_int, c_int, c_int, c_int, P, P]),
+    "fv_subsample2_bwd": (c_int, [c_int, P, c_int, c_int, c_int, c_int, P, P]),
+    "fv_bn2_add_relu_fwd": (c_int, [c_int, P, P, P, P, P, P, c_long, c_int, P, P]),
+    "fv_add2": (c_int, [c_int, P, P, c_long, P, P]),
+    "fv_pose_pool_fwd": (c_int, [c_int, P, c_int, c_int, c_int, P, P]),
+    "fv_pose_head_fwd": (c_int, [P, c_int, c_int, c_int, P, P, P, P, P]),
+    "fv_pose_head_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "fv_pose_head_bwd": (c_int, [c_int, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P]),
 }
 
 _lib = None

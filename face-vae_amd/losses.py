@@ -1,6 +1,8 @@
 """Loss modules with the reference call signatures (losses.py of Luh1124/face-vae)."""
 from __future__ import annotations
 
+import math
+
 import torch
 from torch import nn
 
@@ -61,6 +63,16 @@ class FeatureMatchingLoss(nn.Module):
             t = ops.l1_loss(f, r.detach()) * (f.shape[0] / num_d)
             loss = t if loss is None else loss + t
         return loss
+
+
+class HeadPoseLoss(nn.Module):
+    """losses.py:224-231: the mean of the three L1 distances between the estimated and the
+    (detached) teacher angles, in degrees.  [N] tensors: plain torch ops on any device."""
+
+    def forward(self, yaw, pitch, roll, real_yaw, real_pitch, real_roll):
+        loss = ((yaw - real_yaw.detach()).abs().mean() + (pitch - real_pitch.detach()).abs().mean()
+                + (roll - real_roll.detach()).abs().mean()) / 3
+        return loss / math.pi * 180
 
 
 from .perceptual import PerceptualLoss  # noqa: E402,F401  (losses.py:123-151)

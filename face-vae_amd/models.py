@@ -9,8 +9,8 @@ from torch import nn
 from . import config as _config
 from . import ops
 from . import ops3d, warp
-from .modules import (Conv2d, Conv3d, ConvBlock2D, DownBlock2D, DownBlock3D, ResBlock2D, ResBlock3D, UpBlock2D,
-                      UpBlock3D, _Block)
+from .modules import (Conv2d, Conv3d, ConvBlock2D, DownBlock2D, DownBlock3D, MaxPool2d, ResBlock2D, ResBlock3D,
+                      ResBottleneck, UpBlock2D, UpBlock3D, _Block)
 
 
 def _batched_weight_prep(model, device):
@@ -114,6 +114,68 @@ class MFE(_Block):
         deformation, mask = warp.deformation_from_mask(mask_logits, sparse_motion)
         occlusion = self.occlusion_conv(ops3d.depth_merge(x, mode), sigmoid=True)   # models.py:1080-1081
         return deformation, occlusion, mask
+
+
+class HPE_EDE(_Block):
+    """Head pose estimator (models.py:990-1037): a ResNet-50-shaped trunk -- `pre_layers` (7x7
+    stride-2 stem CNA, MaxPool2d(3, 2, 1)), `res_layers` (ResBottleneck chains, the first of every
+    chain but the first at stride 2) -- then the mean over the plane and five Linear heads; the
+    angles are the softmax expectation over n_bins 3-degree bins.  forward(x) -> (yaw [N],
+    pitch [N], roll [N], t [N, 3], scale [N, 1, 1, 1]), all fp32; x is the NCHW fp32 image on the
+    GPU and gets no gradient.  Reference constructor signature, state-dict keys and init draws
+    (`K` is unused there too; `idx_tensor` is not a buffer).  H and W must be even at every
+    strided stage (a multiple of 32 for the default depth)."""
+
+    def __init__(self, use_weight_norm=False, n_filters=[64, 256, 512, 1024, 2048], n_blocks=[3, 3, 5, 2], n_bins=66,
+                 K=15):
+        super().__init__()
+        if use_weight_norm:
+            raise NotImplementedError("facevae_amd HPE_EDE: use_weight_norm=False only (no spectral norm on the "
+                                      "stem, stride-2 and 'CN' blocks)")
+        n_filters, n_blocks = list(n_filters), list(n_blocks)
+        self.pre_layers = nn.Sequential(ConvBlock2D("CNA", 3, n_filters[0], 7, 2, 3, use_weight_norm), MaxPool2d(3, 2, 1))
+        res_layers = []
+        for i in range(len(n_filters) - 1):
+            res_layers.extend(self._make_layer(i, n_filters[i], n_filters[i + 1], n_blocks[i], use_weight_norm))
+        self.res_layers = nn.Sequential(*res_layers)
+        self.fc_yaw = nn.Linear(n_filters[-1], n_bins)
+        self.fc_pitch = nn.Linear(n_filters[-1], n_bins)
+        self.fc_roll = nn.Linear(n_filters[-1], n_bins)
+        self.fc_t = nn.Linear(n_filters[-1], 3)
+        self.fc_scale = nn.Linear(n_filters[-1], 1)
+        self.n_bins = n_bins
+
+    @staticmethod
+    def _make_layer(i, in_channels, out_channels, n_block, use_weight_norm):
+        stride = 1 if i == 0 else 2
+        return [ResBottleneck(in_channels, out_channels, stride, use_weight_norm)] + [
+            ResBottleneck(out_channels, out_channels, 1, use_weight_norm) for _ in range(n_block)]
+
+    def _check_sizes(self, H, W):
+        stages = [("pre_layers.0 (7x7 stride-2 stem)", 2), ("pre_layers.1 (MaxPool2d(3, 2, 1))", 2)]
+        stages += [(f"res_layers.{i} (stride-2 ResBottleneck)", b.stride) for i, b in enumerate(self.res_layers)]
+        h, w = H, W
+        for name, stride in stages:
+            if stride != 2:
+                continue
+            if h % 2 or w % 2:
+                raise ValueError(f"facevae_amd HPE_EDE: {name} needs an even input size, got {h} x {w} "
+                                 f"(image {H} x {W})")
+            h, w = h // 2, w // 2
+
+    def forward(self, x):
+        if not x.is_cuda:
+            raise RuntimeError("facevae_amd ops run on the GPU only (HIP); got a CPU tensor")
+        from . import ops_pose
+        self._check_sizes(x.shape[2], x.shape[3])
+        _batched_weight_prep(self, x.device)
+        stem = self.pre_layers[0]
+        h = ops_pose.StemFn.apply(x, stem.conv.weight, stem.conv.bias, stem.bn.weight, stem.bn.bias, stem, True)
+        h = self.res_layers(h)
+        fcs = (self.fc_yaw, self.fc_pitch, self.fc_roll, self.fc_t, self.fc_scale)
+        wb = [p for fc in fcs for p in (fc.weight, fc.bias)]
+        out = ops_pose.PoseHeadFn.apply(h, self.n_bins, ops.storage(self.compute_dtype()), *wb)
+        return out[:, 0], out[:, 1], out[:, 2], out[:, 3:6], out[:, 6].view(-1, 1, 1, 1)
 
 
 class Generator(_Block):

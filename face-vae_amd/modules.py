@@ -139,7 +139,12 @@ class ConvBlock2D(_Block):
     The patch discriminator's blocks (models.py:1120-1127) are accepted too: "CNA" with
     activation_type "instance" (conv -> InstanceNorm2d(affine) -> act) at stride 1 or at stride 2
     with a 3x3 kernel and padding 1 (ops.ConvINActFn), and "CN" with activation_type "none" (a
-    plain conv, ops.ConvFn)."""
+    plain conv, ops.ConvFn).
+
+    The head pose estimator's blocks (models.py:1003, modules.py:143-147), with activation_type
+    "batch" and no spectral norm only: the stem "CNA" 3 -> cout 7x7 at stride 2 with padding 3
+    (ops_pose.StemFn), "CNA" 3x3 at stride 2 with padding 1, and "CN" (conv -> BN, no activation)
+    1x1 at stride 1 or 2 (ops_pose.ConvBNFn)."""
 
     def __init__(self, pattern, in_channels, out_channels, kernel_size, stride, padding, use_weight_norm,
                  activation_type="batch", nonlinearity_type="relu"):
@@ -148,6 +153,10 @@ class ConvBlock2D(_Block):
         if activation_type in ("instance", "none"):
             self._init_disc(pattern, in_channels, out_channels, kernel_size, stride, padding, use_weight_norm,
                             activation_type, nonlinearity_type)
+            return
+        form = self._pose_form(pattern, in_channels, kernel_size, stride, padding)
+        if activation_type == "batch" and not use_weight_norm and form is not None:
+            self._init_pose(form, pattern, in_channels, out_channels, kernel_size, nonlinearity_type)
             return
         if stride != 1 or padding != kernel_size // 2:
             raise NotImplementedError("facevae_amd ConvBlock2D: stride 1, 'same' padding only")
@@ -165,6 +174,35 @@ class ConvBlock2D(_Block):
         _ref(self, "bn", mappings["N"])
         _ref(self, "act", mappings["A"])
         self.slope = self.act.slope
+        self.upsample = False
+        self.pool = False
+
+    @staticmethod
+    def _pose_form(pattern, in_channels, kernel_size, stride, padding):
+        if (pattern, in_channels, kernel_size, stride, padding) == ("CNA", 3, 7, 2, 3):
+            return "STEM"
+        if (pattern, kernel_size, stride, padding) == ("CNA", 3, 2, 1):
+            return "CNA_S2"
+        if (pattern, kernel_size, padding) == ("CN", 1, 0) and stride in (1, 2):
+            return "CBN"
+        return None
+
+    def _init_pose(self, form, pattern, in_channels, out_channels, kernel_size, nonlinearity_type):
+        if not (ops.is_pow2_8(out_channels) and out_channels <= 2048):
+            raise NotImplementedError("facevae_amd ConvBlock2D: batch norm needs 8 * a power of two channels, at most "
+                                      f"2048 (got {out_channels})")
+        self.pattern = form
+        # same RNG draws as the reference: nn.Conv2d.reset_parameters; SyncBatchNorm draws nothing
+        mappings = {"C": _Conv(in_channels, out_channels, kernel_size, False),
+                    "N": _BatchNorm(out_channels)}
+        if "A" in pattern:
+            mappings["A"] = _Act(nonlinearity_type)
+        self.layers = nn.Sequential(*[mappings[c] for c in pattern])
+        _ref(self, "conv", mappings["C"])
+        _ref(self, "bn", mappings["N"])
+        if "A" in pattern:
+            _ref(self, "act", mappings["A"])
+        self.slope = self.act.slope if "A" in pattern else 1.0     # slope 1: the identity activation
         self.upsample = False
         self.pool = False
 
@@ -198,6 +236,13 @@ class ConvBlock2D(_Block):
         self.pool = False
 
     def forward(self, x):
+        if self.pattern == "STEM":
+            from . import ops_pose
+            return ops_pose.StemFn.apply(x, self.conv.weight, self.conv.bias, self.bn.weight, self.bn.bias, self,
+                                         False)
+        if self.pattern in ("CNA_S2", "CBN"):
+            from . import ops_pose
+            return ops_pose.ConvBNFn.apply(x, self.conv.weight, self.conv.bias, self.bn.weight, self.bn.bias, self)
         if self.pattern == "CIA":
             return ops.ConvINActFn.apply(x, self.conv.weight_param(), self.conv.bias, self.bn.weight, self.bn.bias, self)
         if self.pattern == "CN":
@@ -278,6 +323,63 @@ class ResBlock2D(_Block):
             out._fv_q8_consumer = q8                  # fp8: the conv consuming out's gradient
             self._fv_q8_consumer = None
         return out
+
+
+class MaxPool2d(_Block):
+    """nn.MaxPool2d(3, 2, 1) stand-in (HPE_EDE.pre_layers[1], models.py:1003): no parameters, so
+    no state-dict keys.  Even H and W, channels a multiple of 8 (ops_pose.MaxPool3s2Fn); inside
+    HPE_EDE it is fused into the stem's BN / activation pass instead."""
+
+    def __init__(self, kernel_size=3, stride=2, padding=1):
+        super().__init__()
+        if (kernel_size, stride, padding) != (3, 2, 1):
+            raise NotImplementedError("facevae_amd MaxPool2d: kernel_size 3, stride 2, padding 1 only")
+
+    def extra_repr(self):
+        return "kernel_size=3, stride=2, padding=1"
+
+    def forward(self, x):
+        from . import ops_pose
+        return ops_pose.MaxPool3s2Fn.apply(x, ops.storage(self.compute_dtype()))
+
+
+class ResBottleneck(_Block):
+    """relu(down_sample(x) + layers(x)) (modules.py:138-152): layers = CNA 1x1 -> CNA 3x3 (stride)
+    -> CN 1x1 with out_channels // 4 channels in between; down_sample = CN 1x1 (stride) when the
+    stride or the channel count changes, else the identity.  Reference state-dict keys
+    (down_sample.layers.{0,1}.*, layers.{0,1,2}.layers.{0,1}.*) and RNG draw order (down_sample
+    is built first).  One autograd Function (ops_pose.BottleneckFn); the two "CN" batch norms run
+    inside the join.  out_channels // 4 must be 8 * a power of two; stride 2 needs even H, W."""
+
+    def __init__(self, in_channels, out_channels, stride, use_weight_norm):
+        super().__init__()
+        if use_weight_norm:
+            raise NotImplementedError("facevae_amd ResBottleneck: use_weight_norm=False only")
+        if stride not in (1, 2):
+            raise NotImplementedError("facevae_amd ResBottleneck: stride 1 or 2")
+        mid = out_channels // 4
+        if out_channels % 4 or not ops.is_pow2_8(mid):
+            raise NotImplementedError("facevae_amd ResBottleneck: out_channels // 4 must be 8 * a power of two "
+                                      f"(got out_channels={out_channels})")
+        self.stride = stride
+        self.project = stride != 1 or in_channels != out_channels
+        self.down_sample = _Identity()
+        if self.project:
+            self.down_sample = ConvBlock2D("CN", in_channels, out_channels, 1, stride, 0, use_weight_norm)
+        self.layers = nn.Sequential(
+            ConvBlock2D("CNA", in_channels, mid, 1, 1, 0, use_weight_norm),
+            ConvBlock2D("CNA", mid, mid, 3, stride, 1, use_weight_norm),
+            ConvBlock2D("CN", mid, out_channels, 1, 1, 0, use_weight_norm),
+        )
+        self.relu = _Act("relu")
+
+    def forward(self, x):
+        from . import ops_pose
+        blocks = list(self.layers) + ([self.down_sample] if self.project else [])
+        params = []
+        for b in blocks:
+            params += [b.conv.weight, b.conv.bias, b.bn.weight, b.bn.bias]
+        return ops_pose.BottleneckFn.apply(x, self, *params)
 
 
 class _Conv3(nn.Module):

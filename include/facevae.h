@@ -31,6 +31,11 @@
  *                           compress / mask_conv (models.py:1054, 1057): general-channel implicit GEMM.
  *   fv_grid_sample3d_*, fv_occlusion_*, fv_sparse_motion_*, fv_heatmap_*, fv_motion_mask_*
  *                            warp path: models.py:1076-1078,1103,1106; utils.py:123-179.
+ *   fv_stem7s2_*, fv_maxpool3s2_*   HPE_EDE.pre_layers (models.py:1003): the 7x7 stride-2 stem conv and
+ *                            nn.MaxPool2d(3, 2, 1).
+ *   fv_subsample2_*, fv_bn2_add_relu_fwd   ResBottleneck (modules.py:138-152): the stride of its
+ *                            stride-2 1x1 convs and relu(down_sample(x) + layers(x)).
+ *   fv_pose_pool_fwd, fv_pose_head_*   torch.mean, fc_*, softmax expectation (models.py:1025-1036).
  *   fv_adam_step             torch.optim.Adam(lr, betas=(0.5,0.999)) (logger.py:60-61).
  *   fv_comm_*                distributed.py:24-31 init_process_group("nccl") + DDP's
  *                            gradient all-reduce (logger.py:55,58) + SyncBN collectives.
@@ -693,6 +698,71 @@ int fv_in_act_bwd_apply(int dtype, const void* dout, const void* x, int n, int h
  * gy = 2 h / (H - 1) - 1; the padding channels 0.  h, w >= 2. */
 int fv_disc_input_fwd(int dtype, const float* img, const float* kp, int n, int h, int w, int k, int kp_stride, int ldc,
                       void* out, void* stream);
+
+/* ------------------------------------------------------ head pose estimator pieces ---- */
+/* The operators of HPE_EDE (models.py:990-1037; ResBottleneck modules.py:138-152) that the 1x1 /
+ * 3x3 convolution and batch-norm entries above do not cover.  dtype FV_F32 (exact) or FV_BF16
+ * (fp32 accumulation).  Every cross-thread sum has a fixed order and no float atomics: reruns are
+ * bit-identical.  Unsupported shapes return FV_E_UNSUPPORTED (the size queries return 0).
+ *
+ * Stem: nn.Conv2d(3, cout, 7, 2, 3) of pre_layers[0] (models.py:1003) as an implicit GEMM on the
+ * matrix units.  x is the NCHW fp32 image [n][3][h][w], read directly (rounded to bf16 in bf16
+ * mode); h and w even; y is NHWC [n][h/2][w/2][cout] of `dtype`, cout a multiple of 8.  wk is the
+ * weight image [cout rounded up to 16][160] of `dtype` with k = (r*7 + s)*3 + ci (147 valid
+ * columns, the rest zero), written by fv_stem7s2_weight_prep from the parameter [cout][3][7][7].
+ * stats (may be NULL): fv_stem7s2_stats_blocks records [2][cout] of (sum, sum of squares) over
+ * fv_stem7s2_stats_block_pixels pixels each of the fp32 pre-rounding outputs (bias included),
+ * the layout fv_bn_stats_finalize_partials consumes.  bwd_weight: dw [cout][3][7][7] and db
+ * [cout] (db may be NULL) from dy NHWC [n][h/2][w/2][cout]; the pixels are split into fp32 slabs
+ * in ws (fv_stem7s2_wgrad_ws_bytes) that are summed in split order.
+ * There is NO data gradient: the stem's input is the image, which is data (trainer.py:272-273). */
+size_t fv_stem7s2_wk_elems(int cout);
+int fv_stem7s2_weight_prep(int dtype, const float* w, int cout, void* wk, void* stream);
+int fv_stem7s2_stats_blocks(int n, int h, int w);
+int fv_stem7s2_stats_block_pixels(void);
+int fv_stem7s2_fwd(int dtype, const float* x, int n, int h, int w, int cout, const void* wk, const float* bias,
+                   void* y, float* stats, void* stream);
+size_t fv_stem7s2_wgrad_ws_bytes(int n, int h, int w, int cout);
+int fv_stem7s2_bwd_weight(int dtype, const float* x, const void* dy, int n, int h, int w, int cout, float* dw,
+                          float* db, void* ws, void* stream);
+/* nn.MaxPool2d(3, 2, 1) (models.py:1003) over dense NHWC [n][h][w][c], h and w even, c a multiple
+ * of 8; padding behaves as -inf.  argmax [n][h/2][w/2][c] uint8: the winning tap 0..8 in row-major
+ * window order (input pixel (2 oy - 1 + tap / 3, 2 ox - 1 + tap % 3)); the first in-bounds tap wins
+ * ties and NaN propagates, as torch's `val > maxval || isnan(val)`.  With scale != NULL the pooled
+ * value is act(x * scale[c] + shift[c]) rounded to `dtype` (the expression and rounding of
+ * fv_bn_act_fwd, slope in [0, 1]).  bwd is a gather: dx [n][h][w][c], every element written, is the
+ * sum of g over the (at most four) windows whose argmax is that element, in window order; with
+ * the prologue it is the gradient with respect to the activation output. */
+int fv_maxpool3s2_fwd(int dtype, const void* x, int n, int h, int w, int c, const float* scale, const float* shift,
+                      float slope, void* y, uint8_t* argmax, void* stream);
+int fv_maxpool3s2_bwd(int dtype, const void* g, const uint8_t* argmax, int n, int h, int w, int c, void* dx,
+                      void* stream);
+/* y[n][i][j][c] = x[n][2i][2j][c] (the stride of ResBottleneck's stride-2 1x1 convs, modules.py:143);
+ * bwd: dx = g at the even pixels, 0 elsewhere, every element written.  h, w even, c % 8 == 0. */
+int fv_subsample2_fwd(int dtype, const void* x, int n, int h, int w, int c, void* y, void* stream);
+int fv_subsample2_bwd(int dtype, const void* g, int n, int h, int w, int c, void* dx, void* stream);
+/* Bottleneck join (modules.py:152): out = relu(ya * sa[c] + ha[c] + (sb ? yb * sb[c] + hb[c] : yb))
+ * over `pixels` x c dense NHWC elements, c % 8 == 0. */
+int fv_bn2_add_relu_fwd(int dtype, const void* ya, const float* sa, const float* ha, const void* yb, const float* sb,
+                        const float* hb, long pixels, int c, void* out, void* stream);
+/* out = a + b over n elements (n % 8 == 0; out aliases neither input): the block-input gradient of a
+ * ResBottleneck is the sum of its two branches' gradients, and no existing addend slot sits there
+ * (the BN apply's addend is at the BN input, which has out_channels / 4 channels). */
+int fv_add2(int dtype, const void* a, const void* b, long n, void* out, void* stream);
+/* Pose head (models.py:1025-1036).  pool: feat [n][c] fp32 = mean over the hw plane of x NHWC
+ * [n][hw][c].  head_fwd: w / b are HOST arrays of five device pointers (fc_yaw, fc_pitch, fc_roll,
+ * fc_t, fc_scale: [rows][c] and [rows] fp32 with rows n_bins, n_bins, n_bins, 3, 1); out [n][7] =
+ * (yaw, pitch, roll, t0, t1, t2, scale) with angle = (sum_j j p_j - n_bins / 2) * 3 pi / 180 and p
+ * the softmax of the head's logits, saved in prob [n][3][n_bins].  head_bwd: from g_out [n][7],
+ * dw / db (HOST arrays of five device pointers, summed over the samples in order) and dx NHWC
+ * [n][hw][c] of `dtype` = dfeat / hw broadcast over the plane; ws: fv_pose_head_ws_bytes. */
+int fv_pose_pool_fwd(int dtype, const void* x, int n, int hw, int c, float* feat, void* stream);
+int fv_pose_head_fwd(const float* feat, int n, int c, int n_bins, const float* const* w, const float* const* b,
+                     float* out, float* prob, void* stream);
+size_t fv_pose_head_ws_bytes(int n, int c, int n_bins);
+int fv_pose_head_bwd(int dtype, const float* g_out, const float* feat, const float* prob, int n, int hw, int c,
+                     int n_bins, const float* const* w, float* const* dw, float* const* db, void* dx, void* ws,
+                     void* stream);
 
 #ifdef __cplusplus
 }
