@@ -9,21 +9,22 @@ through the C-ABI in include/facevae.h.
 """
 from . import _lib
 from .config import FaceVAEConfig, compute_dtype, set_compute_dtype
-from .losses import (FeatureMatchingLoss, GANLoss, HeadPoseLoss, KLDivergenceLoss, L1Loss, PerceptualLoss,
-                     ReconLoss)
-from .models import AFE, HPE_EDE, MFE, Discriminator, FaceVAE, Generator
+from .losses import (DeformationPriorLoss, EquivarianceLoss, FeatureMatchingLoss, GANLoss, HeadPoseLoss,
+                     KeypointPriorLoss, KLDivergenceLoss, L1Loss, PerceptualLoss, ReconLoss)
+from .models import AFE, CKD, HPE_EDE, MFE, Discriminator, FaceVAE, Generator
 from .modules import (Conv2d, Conv3d, ConvBlock2D, ConvBlock3D, ConvTranspose2dELR, DownBlock2D, DownBlock3D,
                       MaxPool2d, ResBlock2D, ResBlock3D, ResBottleneck, SameBlock2D, UpBlock2D, UpBlock3D)
 from .optim import Adam
 from .pose import rotation_matrix_x, rotation_matrix_y, rotation_matrix_z, transform_kp
-from . import checkpoint, distributed, graph, ops, ops3d, ops_pose, pose, warp
+from . import checkpoint, distributed, graph, ops, ops3d, ops_ckd, ops_pose, pose, warp
 from .graph import StepGraph
 
 __all__ = ["FaceVAEConfig", "compute_dtype", "set_compute_dtype", "KLDivergenceLoss", "L1Loss", "PerceptualLoss", "ReconLoss",
            "AFE", "FaceVAE", "Generator", "Conv2d", "ConvBlock2D", "ConvTranspose2dELR", "DownBlock2D", "ResBlock2D", "ResBlock3D", "ConvBlock3D", "SameBlock2D",
            "UpBlock2D", "Adam", "distributed", "ops", "FaceVAETrainer", "Discriminator", "GANLoss", "FeatureMatchingLoss",
            "MFE", "DownBlock3D", "UpBlock3D", "Conv3d", "HPE_EDE", "ResBottleneck", "MaxPool2d", "HeadPoseLoss",
-           "transform_kp", "rotation_matrix_x", "rotation_matrix_y", "rotation_matrix_z", "ops_pose", "pose"]
+           "transform_kp", "rotation_matrix_x", "rotation_matrix_y", "rotation_matrix_z", "ops_pose", "pose",
+           "CKD", "EquivarianceLoss", "KeypointPriorLoss", "DeformationPriorLoss", "ops_ckd"]
 
 
 def __getattr__(name):

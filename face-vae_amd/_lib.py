@@ -254,6 +254,10 @@ _SIGS = {
     "fv_pose_head_fwd": (c_int, [P, c_int, c_int, c_int, P, P, P, P, P]),
     "fv_pose_head_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "fv_pose_head_bwd": (c_int, [c_int, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P]),
+    "fv_ckd_resize_fwd": (c_int, [c_int, P, c_int, c_int, c_int, c_int, c_int, P, P]),
+    "fv_ckd_softargmax_ws_bytes": (c_size_t, [c_int] * 5),
+    "fv_ckd_softargmax_fwd": (c_int, [c_int, P, c_int, c_int, c_int, c_int, c_int, c_float, P, P, P, P]),
+    "fv_ckd_softargmax_bwd": (c_int, [c_int, P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, P, P]),
 }
 
 _lib = None

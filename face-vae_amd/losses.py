@@ -75,4 +75,37 @@ class HeadPoseLoss(nn.Module):
         return loss / math.pi * 180
 
 
+class EquivarianceLoss(nn.Module):
+    """losses.py:198-205: mean |kp_d[..., :2] - reverse_kp|, the detected keypoints of a warped
+    image against the warp applied to the original's.  [N, K, 3] and [N, K, 2] tensors: plain torch
+    ops on any device."""
+
+    def forward(self, kp_d, reverse_kp):
+        return (kp_d[:, :, :2] - reverse_kp).abs().mean()
+
+
+class KeypointPriorLoss(nn.Module):
+    """losses.py:208-221: keypoints closer than sqrt(Dt) repel (a hinge on the squared pairwise
+    distances, the K diagonal terms of Dt each subtracted again) and the mean depth is pulled to
+    zt.  The distances are torch.cdist(...).square(), not a squared difference: the gradient at the
+    zero diagonal is then what torch gives the reference.  Plain torch ops on any device."""
+
+    def __init__(self, Dt=0.1, zt=0.33):
+        super().__init__()
+        self.Dt, self.zt = Dt, zt
+
+    def forward(self, kp_d):
+        dist = torch.cdist(kp_d, kp_d).square()
+        hinge = torch.max(0 * dist, self.Dt - dist).sum((1, 2)).mean()
+        depth = (kp_d[:, :, 2].mean(1) - self.zt).abs().mean()
+        return hinge + depth - kp_d.shape[1] * self.Dt
+
+
+class DeformationPriorLoss(nn.Module):
+    """losses.py:234-240: mean |delta_d| of the expression deformations.  Plain torch ops."""
+
+    def forward(self, delta_d):
+        return delta_d.abs().mean()
+
+
 from .perceptual import PerceptualLoss  # noqa: E402,F401  (losses.py:123-151)

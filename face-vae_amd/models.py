@@ -178,6 +178,94 @@ class HPE_EDE(_Block):
         return out[:, 0], out[:, 1], out[:, 2], out[:, 3:6], out[:, 6].view(-1, 1, 1, 1)
 
 
+class CKD(_Block):
+    """Canonical keypoint detector (models.py:948-987): the image resized by `scale_factor`
+    (bilinear), a DownBlock2D chain, the 1x1 `mid_conv` to C * D channels, x.view(N, C, D, H, W), an
+    UpBlock3D chain, the 3x3x3 `out_conv` to K logit volumes, and the softmax expectation of the
+    coordinate grid at temperature 0.1 (utils.py:106-118).  forward(x) -> kp [N, K, 3] fp32 in
+    [-1, 1], (x, y, z) = (along W, along H, along D); x is the NCHW fp32 image on the GPU and gets
+    no gradient.  Reference constructor signature, state-dict keys and init draws.
+
+    The resize writes the first conv's input directly (ops_ckd.ResizeFn) and the soft-argmax never
+    materialises the heatmap (ops_ckd.SoftArgmaxFn, csrc/ckd.hip); everything between runs on the
+    2-D conv / BN kernels, fv_depth_split and the general 3-D conv kernels of the MFE's up stack.
+    The resized image must stay even through every DownBlock2D (a multiple of 32 for the default
+    depth, i.e. an image that is a multiple of 128 at scale 0.25).  fp8 mode runs in bf16."""
+
+    def __init__(self, use_weight_norm=False, down_seq=[3, 64, 128, 256, 512, 1024],
+                 up_seq=[1024, 512, 256, 128, 64, 32], D=16, K=15, scale_factor=0.25):
+        super().__init__()
+        if use_weight_norm:
+            raise NotImplementedError("facevae_amd CKD: use_weight_norm=False only (no spectral norm on 3-D convs)")
+        down_seq, up_seq = list(down_seq), list(up_seq)
+        if down_seq[0] != 3:
+            raise NotImplementedError(f"facevae_amd CKD: down_seq[0] must be 3, the image (got {down_seq[0]})")
+        for c in down_seq[1:]:
+            if not (ops.is_pow2_8(c) and c <= 2048):
+                raise NotImplementedError("facevae_amd CKD: the batch-norm kernels take 8 * a power of two channels, at "
+                                          f"most 2048 (down_seq has {c})")
+        if not ops.is_pow2_8(up_seq[0] * D):
+            raise NotImplementedError("facevae_amd CKD: the depth split reads a dense NHWC tensor, so up_seq[0] * D must "
+                                      f"be 8 * a power of two (got {up_seq[0]} * {D})")
+        for c in up_seq:
+            if c % 8 or ops.pad_pow2(c) > 2048:
+                raise NotImplementedError("facevae_amd CKD: the 3-D conv kernels take input channels in multiples of 8 "
+                                          f"and the batch norm at most 2048 (up_seq has {c})")
+        if D < 2:
+            raise NotImplementedError(f"facevae_amd CKD: D must be at least 2, the depth coordinate divides by D - 1 (got {D})")
+        if not 1 <= K <= 256:
+            raise NotImplementedError(f"facevae_amd CKD: the soft-argmax kernel takes 1 <= K <= 256 (got {K})")
+        self.down = nn.Sequential(*[DownBlock2D(down_seq[i], down_seq[i + 1], use_weight_norm)
+                                    for i in range(len(down_seq) - 1)])
+        self.mid_conv = Conv2d(down_seq[-1], up_seq[0] * D, 1, 1, 0)
+        self.up = nn.Sequential(*[UpBlock3D(up_seq[i], up_seq[i + 1], use_weight_norm)
+                                  for i in range(len(up_seq) - 1)])
+        self.out_conv = Conv3d(up_seq[-1], K, 3, 1, 1)
+        self.C, self.D = up_seq[0], D
+        self.scale_factor = scale_factor
+        self.temperature = 0.1                      # out2heatmap's default, utils.py:106
+
+    def _check_sizes(self, H, W):
+        from . import ops_ckd
+        h, w = ops_ckd.resized(H, self.scale_factor), ops_ckd.resized(W, self.scale_factor)
+        if h < 1 or w < 1:
+            raise ValueError(f"facevae_amd CKD: image {H} x {W} at scale {self.scale_factor} leaves no pixel")
+        for i in range(len(self.down)):
+            if h % 2 or w % 2:
+                raise ValueError(f"facevae_amd CKD: down.{i} (DownBlock2D, AvgPool2d(2)) needs an even input size, got "
+                                 f"{h} x {w} (image {H} x {W} resized by {self.scale_factor})")
+            h, w = h // 2, w // 2
+        if (h << len(self.up)) < 2 or (w << len(self.up)) < 2:
+            raise ValueError(f"facevae_amd CKD: the heatmap of image {H} x {W} is below 2 x 2 (the coordinate grid "
+                             "divides by size - 1)")
+
+    def forward(self, x):
+        if not x.is_cuda:
+            raise RuntimeError("facevae_amd ops run on the GPU only (HIP); got a CPU tensor")
+        from . import ops_ckd
+        self._check_sizes(x.shape[2], x.shape[3])
+        mode = self.compute_dtype()
+        if mode == ops.FP8:
+            # no fp8 path through the 3-D convs: the whole module runs in bf16 for this forward
+            # (the backward reads what the forward stored, not the modules' mode)
+            saved = [(m, m._dtype) for m in self.modules() if hasattr(m, "_dtype")]
+            self.set_compute_dtype(torch.bfloat16)
+            try:
+                return self._forward(x, torch.bfloat16, ops_ckd)
+            finally:
+                for m, d in saved:
+                    m._dtype = d
+        return self._forward(x, mode, ops_ckd)
+
+    def _forward(self, x, mode, ops_ckd):
+        _batched_weight_prep(self, x.device)
+        h = ops_ckd.ResizeFn.apply(x, self.scale_factor, ops.storage(mode))
+        h = self.mid_conv(self.down(h))
+        v = ops3d.depth_split(h, self.C, self.D, mode)            # x.view(N, C, D, H, W), models.py:982
+        z = self.out_conv(self.up(v))
+        return ops_ckd.SoftArgmaxFn.apply(z, self.temperature)
+
+
 class Generator(_Block):
     """Decoder (models.py:1085-1111): grid_sample of the 3-D appearance volume by the motion
     field (1103, warp.grid_sample_3d), view to [N, C*D, H, W], in_conv (SN, LeakyReLU .2),

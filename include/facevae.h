@@ -764,6 +764,36 @@ int fv_pose_head_bwd(int dtype, const float* g_out, const float* feat, const flo
                      int n_bins, const float* const* w, float* const* dw, float* const* db, void* dx, void* ws,
                      void* stream);
 
+/* ------------------------------------------------ canonical keypoint detector pieces ---- */
+/* The head and the tail of CKD (models.py:948-987) around the conv / batch-norm entries above.
+ * dtype FV_F32 or FV_BF16 storage, fp32 arithmetic, no float atomics, every cross-thread sum in a
+ * fixed order (reruns are bit-identical).  Unsupported arguments return FV_E_UNSUPPORTED.
+ *
+ * Resize: F.interpolate(x, mode="bilinear", align_corners=False, recompute_scale_factor=True) of the
+ * NCHW fp32 image x [n][3][h][w] to ho x wo (the caller passes floor(h * s), floor(w * s)).  The
+ * sampling scale is h / ho (w / wo) in fp32, the source index scale * (o + 0.5) - 0.5 clamped at
+ * 0, the upper neighbour clamped at the last row / column, and the blend
+ * h0 (w0 a + w1 b) + h1 (w0 c + w1 d).  y is dense NHWC [n][ho][wo][8] of `dtype`: channels 0-2 the
+ * result, 3-7 zero -- the first conv's input with cin_valid = 3.  There is no backward. */
+int fv_ckd_resize_fwd(int dtype, const float* x, int n, int h, int w, int ho, int wo, void* y, void* stream);
+/* Soft-argmax (out2heatmap + heatmap2kp, utils.py:106-118) of the logits z, dense NDHWC
+ * [n][d * h * w][k] of `dtype` (rows of k elements, no alignment assumed):
+ *   kp[n][k][:] = sum_v softmax_v(z[n][v][k] / T) (2 w / (W-1) - 1, 2 h / (H-1) - 1, 2 d / (D-1) - 1)
+ * with the heatmap never written.  d, h, w >= 2; 1 <= k <= 256; d * h * w * k < 2^31.  The maximum
+ * is taken on z and the exponent is (z - max z) / T, so a common offset of the logits costs no
+ * accuracy.  Exponentials, coordinates and products are fp32; the running sums are fp64.  stat
+ * [n][k][8] fp32 = (max_v z, sum_v exp((z - max z) / T), kp hi[3], kp lo[3]) for the backward, hi = kp
+ * and hi + lo the fp64 quotient: at a peaked heatmap kp is within 1e-3 of the peak's coordinate and
+ * the backward's (grid - kp) needs the digits below fp32.  ws: fv_ckd_softargmax_ws_bytes (the
+ * per-chunk partials; 0 for unsupported arguments).
+ * bwd: dz[n][v][k] = (1 / T) p sum_j g_kp[n][k][j] (grid_j(v) - kp[n][k][j]) with
+ * p = exp((z - stat.max) / T) / stat.sum, in `dtype` and the layout of z; every element written. */
+size_t fv_ckd_softargmax_ws_bytes(int n, int k, int d, int h, int w);
+int fv_ckd_softargmax_fwd(int dtype, const void* z, int n, int k, int d, int h, int w, float temperature, float* kp,
+                          float* stat, void* ws, void* stream);
+int fv_ckd_softargmax_bwd(int dtype, const void* z, const float* g_kp, const float* stat, int n, int k, int d, int h,
+                          int w, float temperature, void* dz, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
