@@ -9,14 +9,14 @@ through the C-ABI in include/facevae.h.
 """
 from . import _lib
 from .config import FaceVAEConfig, compute_dtype, set_compute_dtype
-from .losses import (DeformationPriorLoss, EquivarianceLoss, FeatureMatchingLoss, GANLoss, HeadPoseLoss,
+from .losses import (ContrastiveLoss_linear, DeformationPriorLoss, EquivarianceLoss, FeatureMatchingLoss, GANLoss, HeadPoseLoss,
                      KeypointPriorLoss, KLDivergenceLoss, L1Loss, PerceptualLoss, ReconLoss)
-from .models import AFE, CKD, HPE_EDE, MFE, Discriminator, FaceVAE, Generator
+from .models import AFE, CKD, EFE_conv5, HPE_EDE, MFE, Discriminator, FaceVAE, Generator
 from .modules import (Conv2d, Conv3d, ConvBlock2D, ConvBlock3D, ConvTranspose2dELR, DownBlock2D, DownBlock3D,
-                      MaxPool2d, ResBlock2D, ResBlock3D, ResBottleneck, SameBlock2D, UpBlock2D, UpBlock3D)
+                      MaxPool2d, ResBlock2D, ResBlock3D, ResBottleneck, SameBlock2D, SameBlock3D, UpBlock2D, UpBlock3D)
 from .optim import Adam
 from .pose import rotation_matrix_x, rotation_matrix_y, rotation_matrix_z, transform_kp
-from . import checkpoint, distributed, graph, ops, ops3d, ops_ckd, ops_pose, pose, warp
+from . import checkpoint, distributed, graph, ops, ops3d, ops_ckd, ops_efe, ops_pose, pose, warp
 from .graph import StepGraph
 
 __all__ = ["FaceVAEConfig", "compute_dtype", "set_compute_dtype", "KLDivergenceLoss", "L1Loss", "PerceptualLoss", "ReconLoss",
@@ -24,7 +24,8 @@ __all__ = ["FaceVAEConfig", "compute_dtype", "set_compute_dtype", "KLDivergenceL
            "UpBlock2D", "Adam", "distributed", "ops", "FaceVAETrainer", "Discriminator", "GANLoss", "FeatureMatchingLoss",
            "MFE", "DownBlock3D", "UpBlock3D", "Conv3d", "HPE_EDE", "ResBottleneck", "MaxPool2d", "HeadPoseLoss",
            "transform_kp", "rotation_matrix_x", "rotation_matrix_y", "rotation_matrix_z", "ops_pose", "pose",
-           "CKD", "EquivarianceLoss", "KeypointPriorLoss", "DeformationPriorLoss", "ops_ckd"]
+           "CKD", "EquivarianceLoss", "KeypointPriorLoss", "DeformationPriorLoss", "ops_ckd",
+           "EFE_conv5", "SameBlock3D", "ContrastiveLoss_linear", "ops_efe"]
 
 
 def __getattr__(name):

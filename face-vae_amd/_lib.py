@@ -258,6 +258,9 @@ _SIGS = {
     "fv_ckd_softargmax_ws_bytes": (c_size_t, [c_int] * 5),
     "fv_ckd_softargmax_fwd": (c_int, [c_int, P, c_int, c_int, c_int, c_int, c_int, c_float, P, P, P, P]),
     "fv_ckd_softargmax_bwd": (c_int, [c_int, P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, P, P]),
+    "fv_efe_kpcat_fwd": (c_int, [c_int, P, P] + [c_int] * 6 + [c_float, P, P]),
+    "fv_efe_kpcat_ws_bytes": (c_size_t, [c_int] * 6),
+    "fv_efe_kpcat_bwd": (c_int, [c_int, P, P] + [c_int] * 6 + [c_float, P, P, P, P]),
 }
 
 _lib = None

@@ -108,4 +108,45 @@ class DeformationPriorLoss(nn.Module):
         return delta_d.abs().mean()
 
 
+class ContrastiveLoss_linear(nn.Module):
+    """losses.py:243-278, called as ContrastiveLoss_linear(mode=...)(f1, f2) on the two 4 x 4 codes
+    EFE_conv5 returns (x_c, x_a_c; trainer.py:261 uses mode="non-direction").  mode "direction": one
+    minus the mean cosine similarity of the flattened features.  Any other mode: a three-layer
+    `projection` (Linear without bias, BatchNorm1d, ReLU, twice; then Linear with a frozen bias and
+    a BatchNorm1d without affine) and a two-layer `predictor` (Linear without bias, BatchNorm1d, ReLU,
+    Linear), each applied to both inputs, and one minus the mean of the two cosine similarities
+    between a prediction and the other input's detached projection.  Reference signature, state-dict
+    keys (25 by default) and init draws; projection[6].bias.requires_grad is False.
+
+    Plain torch ops on GPU tensors, like KeypointPriorLoss: N x 512 GEMMs on a batch of codes are
+    not a hot path, so there is no HIP kernel here.  The features are flattened in NCHW order
+    whatever their memory layout and computed in fp32.  nn.BatchNorm1d in a single process only:
+    there is no SyncBN for the projector."""
+
+    def __init__(self, in_dim=512, hid_1_dim=512, out_1_dim=512, hid_2_dim=512, out_2_dim=512, mode="direction"):
+        super().__init__()
+        self.criterion = nn.CosineSimilarity(dim=1)
+        self.mode = mode
+        if mode == "direction":
+            return
+        # construction order = the reference's RNG draw order
+        self.projection = nn.Sequential(
+            nn.Linear(in_dim, hid_1_dim, bias=False), nn.BatchNorm1d(hid_1_dim), nn.ReLU(inplace=True),
+            nn.Linear(hid_1_dim, hid_1_dim, bias=False), nn.BatchNorm1d(hid_1_dim), nn.ReLU(inplace=True),
+            nn.Linear(hid_1_dim, out_1_dim, bias=True), nn.BatchNorm1d(out_1_dim, affine=False))
+        self.projection[6].bias.requires_grad = False        # a bias in front of a BN: kept, never trained
+        self.predictor = nn.Sequential(
+            nn.Linear(out_1_dim, hid_2_dim, bias=False), nn.BatchNorm1d(hid_2_dim), nn.ReLU(inplace=True),
+            nn.Linear(hid_2_dim, out_2_dim))
+
+    def forward(self, f1, f2):
+        f1 = f1.float().reshape(f1.shape[0], -1)
+        f2 = f2.float().reshape(f2.shape[0], -1)
+        if self.mode == "direction":
+            return 1 - self.criterion(f1, f2).mean()
+        z1, z2 = self.projection(f1), self.projection(f2)
+        p1, p2 = self.predictor(z1), self.predictor(z2)
+        return 1 - 0.5 * (self.criterion(p1, z2.detach()).mean() + self.criterion(p2, z1.detach()).mean())
+
+
 from .perceptual import PerceptualLoss  # noqa: E402,F401  (losses.py:123-151)

@@ -266,6 +266,150 @@ class CKD(_Block):
         return ops_ckd.SoftArgmaxFn.apply(z, self.temperature)
 
 
+class EFE_conv5(_Block):
+    """Expression feature extractor (models.py:724-799; `EFE` in trainer.py:8): the image resized by
+    `scale_factor`, `down` (SameBlock2D then a DownBlock2D chain) to the 32-channel 4 x 4 code that
+    flatten_vae_nl (models.py:525-570) splits into mu | logstd and reparameterises, the 1x1
+    `mid_conv` of the 16-channel sample to C * D channels, x.view(N, C, D, H, W), `up` (UpBlock3D with
+    a SameBlock3D second to last), the 3x3x3 `out_conv` to K logit volumes, the Gaussians of the
+    posed keypoints `kpc` appended (models.py:790-791), `mix` (ResBlock3D(2K)), `mix_out`
+    (SameBlock3D(2K, K)) and the softmax expectation of the coordinate grid at temperature 0.1.
+
+    forward(x, x_a=None, kpc=None, train_vae=None, eps=None) -> kp [N, K, 3] fp32, x_c, x_a_c,
+    (x_mu, x_logstd), (x_vae, x_hat) as the reference: x_c = down(x) and x_a_c = down(x_a) when x_a is
+    given (the same modules run twice: batch-norm statistics of each pass, num_batches_tracked + 2),
+    else None; x_mu / x_logstd [N, 256] fp32 in NCHW flatten order when train_vae, else None;
+    x_vae = down(x) and x_hat [N, 16, 4, 4] the sample.  `eps` [N, 16, 4, 4] is the noise the
+    reference draws inside flatten_vae_nl (models.py:561), here an input (torch.randn on the device
+    when None).  A following KLDivergenceLoss()((x_mu, x_logstd)) reuses the value the
+    reparameterisation pass reduced.  With train_vae falsy the sample is mu and the logstd channels
+    get a zero gradient.  x and x_a are NCHW fp32 images on the GPU and get no gradient; kpc does.
+
+    The resize and the soft-argmax are CKD's kernels, the concatenation is fv_efe_kpcat_fwd (one
+    launch that also creates the zero pad of the 2K channels to 8 * 2^k), `mix` runs at that padded
+    channel count end to end on the 3x3x3 kernels of the AFE trunk and `mix_out`'s weight gets zero
+    columns for the pad.  Reference constructor signature, state-dict keys and init draws;
+    use_weight_norm=True and use_vae=False raise (the reference's mid_conv takes down_seq[-1] // 2
+    channels, so it cannot run without the VAE either).  fp8 mode runs in bf16."""
+
+    def __init__(self, use_weight_norm=False, down_seq=[3, 32, 64, 128, 256, 32],
+                 up_seq=[256, 256, 128, 64, 32, 32], D=16, K=15, n_res=3, scale_factor=0.25, use_vae=True):
+        super().__init__()
+        from .modules import SameBlock2D, SameBlock3D
+        if use_weight_norm:
+            raise NotImplementedError("facevae_amd EFE_conv5: use_weight_norm=False only (no spectral norm on 3-D "
+                                      "convs)")
+        if not use_vae:
+            raise NotImplementedError("facevae_amd EFE_conv5: use_vae=True only (mid_conv takes down_seq[-1] // 2 "
+                                      "channels, the VAE's sample: the reference cannot run without it either)")
+        down_seq, up_seq = list(down_seq), list(up_seq)
+        if down_seq[0] != 3:
+            raise NotImplementedError(f"facevae_amd EFE_conv5: down_seq[0] must be 3, the image (got {down_seq[0]})")
+        if down_seq[-1] != 32:
+            raise NotImplementedError("facevae_amd EFE_conv5: down_seq[-1] must be 32, the 16 mu and 16 logstd channels "
+                                      f"flatten_vae_nl splits (got {down_seq[-1]})")
+        for c in down_seq[1:]:
+            if not (ops.is_pow2_8(c) and c <= 2048):
+                raise NotImplementedError("facevae_amd EFE_conv5: the batch-norm kernels take 8 * a power of two "
+                                          f"channels, at most 2048 (down_seq has {c})")
+        if not ops.is_pow2_8(up_seq[0] * D):
+            raise NotImplementedError("facevae_amd EFE_conv5: the depth split reads a dense NHWC tensor, so up_seq[0] * D "
+                                      f"must be 8 * a power of two (got {up_seq[0]} * {D})")
+        for c in up_seq:
+            if c % 8 or ops.pad_pow2(c) > 2048:
+                raise NotImplementedError("facevae_amd EFE_conv5: the 3-D conv kernels take input channels in multiples "
+                                          f"of 8 and the batch norm at most 2048 (up_seq has {c})")
+        if D < 2:
+            raise NotImplementedError("facevae_amd EFE_conv5: D must be at least 2, the depth coordinate divides by "
+                                      f"D - 1 (got {D})")
+        if not 1 <= K <= 256:
+            raise NotImplementedError(f"facevae_amd EFE_conv5: the soft-argmax kernel takes 1 <= K <= 256 (got {K})")
+        if ops.pad_pow2(2 * K) > 64:
+            raise NotImplementedError("facevae_amd EFE_conv5: mix runs ResBlock3D at the 2K channels padded to 8 * a "
+                                      f"power of two, at most 64 (got K = {K})")
+        self.down = nn.Sequential(*[SameBlock2D(down_seq[i], down_seq[i + 1], use_weight_norm) if i == 0 else
+                                    DownBlock2D(down_seq[i], down_seq[i + 1], use_weight_norm)
+                                    for i in range(len(down_seq) - 1)])
+        self.mid_conv = Conv2d(down_seq[-1] // 2, up_seq[0] * D, 1, 1, 0)
+        self.up = nn.Sequential(*[SameBlock3D(up_seq[i], up_seq[i + 1], use_weight_norm) if i == len(up_seq) - 2 else
+                                  UpBlock3D(up_seq[i], up_seq[i + 1], use_weight_norm)
+                                  for i in range(len(up_seq) - 1)])
+        self.out_conv = Conv3d(up_seq[-1], K, 3, 1, 1)
+        self.mix = nn.Sequential(*[ResBlock3D(2 * K, use_weight_norm) for _ in range(n_res)])
+        self.mix_out = SameBlock3D(2 * K, K, use_weight_norm)
+        self.C, self.D, self.K = up_seq[0], D, K
+        self.scale_factor = scale_factor
+        self.temperature = 0.1                      # out2heatmap's default, utils.py:106
+        self.kp_variance = 0.01                     # kp2gaussian_3d's default, utils.py:130
+
+    def _check_sizes(self, H, W):
+        from . import ops_ckd
+        h, w = ops_ckd.resized(H, self.scale_factor), ops_ckd.resized(W, self.scale_factor)
+        if h < 1 or w < 1:
+            raise ValueError(f"facevae_amd EFE_conv5: image {H} x {W} at scale {self.scale_factor} leaves no pixel")
+        for i in range(1, len(self.down)):
+            if h % 2 or w % 2:
+                raise ValueError(f"facevae_amd EFE_conv5: down.{i} (DownBlock2D, AvgPool2d(2)) needs an even input "
+                                 f"size, got {h} x {w} (image {H} x {W} resized by {self.scale_factor})")
+            h, w = h // 2, w // 2
+        last = len(self.down) - 1
+        if (h, w) != (4, 4):
+            raise ValueError(f"facevae_amd EFE_conv5: down.{last} leaves {h} x {w}, but the VAE's view(b, 16, 4, 4) "
+                             f"(models.py:564) needs 4 x 4 there: the resized image must be {4 << last} x {4 << last} "
+                             f"(image {H} x {W} resized by {self.scale_factor})")
+
+    def forward(self, x, x_a=None, kpc=None, train_vae=None, eps=None):
+        if not x.is_cuda or (x_a is not None and not x_a.is_cuda) or (kpc is not None and not kpc.is_cuda):
+            raise RuntimeError("facevae_amd ops run on the GPU only (HIP); got a CPU tensor")
+        if kpc is None:
+            raise ValueError("facevae_amd EFE_conv5: the posed keypoints kpc [N, K, 3] are required "
+                             "(kp2gaussian_3d(kpc), models.py:790)")
+        if tuple(kpc.shape) != (x.shape[0], self.K, 3):
+            raise ValueError(f"facevae_amd EFE_conv5: kpc must be [{x.shape[0]}, {self.K}, 3], got {list(kpc.shape)}")
+        self._check_sizes(x.shape[2], x.shape[3])
+        if x_a is not None:
+            self._check_sizes(x_a.shape[2], x_a.shape[3])
+        mode = self.compute_dtype()
+        if mode == ops.FP8:
+            # no fp8 path through the 3-D convs: the whole module runs in bf16 for this forward
+            saved = [(m, m._dtype) for m in self.modules() if hasattr(m, "_dtype")]
+            self.set_compute_dtype(torch.bfloat16)
+            try:
+                return self._forward(x, x_a, kpc, train_vae, eps, torch.bfloat16)
+            finally:
+                for m, d in saved:
+                    m._dtype = d
+        return self._forward(x, x_a, kpc, train_vae, eps, mode)
+
+    def _forward(self, x, x_a, kpc, train_vae, eps, mode):
+        from . import ops_ckd, ops_efe
+        dtype = ops.storage(mode)
+        N = x.shape[0]
+        _batched_weight_prep(self, x.device)
+        h = self.down(ops_ckd.ResizeFn.apply(x, self.scale_factor, dtype))          # [N, 32, 4, 4]
+        x_c = x_a_c = None
+        if x_a is not None:
+            x_c = h
+            x_a_c = self.down(ops_ckd.ResizeFn.apply(x_a, self.scale_factor, dtype))
+        if train_vae:
+            if eps is None:
+                eps = torch.randn(N, 16, 4, 4, device=x.device)
+            mu, ls, z = ops.reparameterise(h, eps, mode)
+            # mu.flatten(start_dim=1) of the NCHW tensor (models.py:559-560); the pair carries the KL
+            # value of the reparameterisation pass like (mu, ls) itself (ops.KLFn)
+            x_mu, x_ls = mu.float().reshape(N, -1), ls.float().reshape(N, -1)
+            x_mu._fv_kl = (x_ls, mu._fv_kl[1], x_mu._version, x_ls._version, mu._fv_kl[4])
+        else:
+            x_mu = x_ls = None
+            z = h[:, :16]               # z = mu; logstd * 0 (models.py:560-561): a zero gradient
+        v = ops3d.depth_split(self.mid_conv(z), self.C, self.D, mode)             # x.view(N, C, D, H, W)
+        logits = self.out_conv(self.up(v))
+        m = ops_efe.KpCatFn.apply(logits, kpc, self.kp_variance)                  # [N, pad_pow2(2K), D, H, W]
+        heat = self.mix_out(self.mix(m))
+        kp = ops_ckd.SoftArgmaxFn.apply(heat, self.temperature)
+        return kp, x_c, x_a_c, (x_mu, x_ls), (h, z)
+
+
 class Generator(_Block):
     """Decoder (models.py:1085-1111): grid_sample of the 3-D appearance volume by the motion
     field (1103, warp.grid_sample_3d), view to [N, C*D, H, W], in_conv (SN, LeakyReLU .2),

@@ -472,6 +472,19 @@ class UpBlock3D(_Block):
         return self.layers[1](x)
 
 
+class SameBlock3D(_Block):
+    """CNA 1x1x1 (modules.py:97-113): on the general 3-D conv kernels.  An input whose channel
+    count is no multiple of 8 is zero-padded on entry; an input that already carries the zero pad
+    to 8 * 2^k channels (EFE_conv5.mix's output) is taken as it is, the weight getting zero columns."""
+
+    def __init__(self, in_channels, out_channels, use_weight_norm):
+        super().__init__()
+        self.layers = ConvBlock3D("CNA", in_channels, out_channels, 1, 1, 0, use_weight_norm)
+
+    def forward(self, x):
+        return self.layers(x)
+
+
 class Conv3d(_Conv3):
     """nn.Conv3d drop-in (stride 1, 'same' padding, kernel 1 / 3 / 7) with state-dict keys weight /
     bias, on the general 3-D conv kernels (ops3d.Conv3dFn); output NDHWC in the storage dtype."""
@@ -492,10 +505,20 @@ class Conv3d(_Conv3):
 
 class ResBlock3D(_Block):
     """x + NAC(NAC(x)) over [N, C, D, H, W] (modules.py:116-126, 133-135): 3x3x3 convs on
-    the HIP kernels of conv3d.hip, BN/ReLU on the NHWC kernels over the NDHWC layout."""
+    the HIP kernels of conv3d.hip, BN/ReLU on the NHWC kernels over the NDHWC layout.
+
+    A channel count that is not 8 * 2^k (EFE_conv5.mix: 2K = 30) runs at pad_pow2(C) <= 64 channels
+    on the same kernels, with the reference parameter shapes and keys: weights, biases and batch
+    norms are zero-padded per forward and the gradients cut back (ops3d.ResBlock3DPadFn).  Such a
+    block takes x with C channels (padded on entry, cut on exit) or with pad_pow2(C) channels whose
+    pad is zero (kept: a chain of them makes no pad or cut copies)."""
 
     def __init__(self, in_channels, use_weight_norm):
         super().__init__()
+        self.padded = not ops.is_pow2_8(in_channels)
+        if self.padded and ops.pad_pow2(in_channels) > 64:
+            raise NotImplementedError("facevae_amd ResBlock3D: the 3x3x3 conv kernels take at most 64 channels "
+                                      f"(got {in_channels}, padded to {ops.pad_pow2(in_channels)})")
         self.layers = nn.Sequential(
             ConvBlock3D("NAC", in_channels, in_channels, 3, 1, 1, use_weight_norm),
             ConvBlock3D("NAC", in_channels, in_channels, 3, 1, 1, use_weight_norm),
@@ -508,8 +531,9 @@ class ResBlock3D(_Block):
     def forward(self, x):
         from . import ops3d
         c1, c2 = self.conv1, self.conv2
-        return ops3d.ResBlock3DFn.apply(x, c1.weight, c1.bias, self.bn1.weight, self.bn1.bias,
-                                        c2.weight, c2.bias, self.bn2.weight, self.bn2.bias, self)
+        fn = ops3d.ResBlock3DPadFn if self.padded else ops3d.ResBlock3DFn
+        return fn.apply(x, c1.weight, c1.bias, self.bn1.weight, self.bn1.bias,
+                        c2.weight, c2.bias, self.bn2.weight, self.bn2.bias, self)
 
 
 class Conv2d(_Conv):

@@ -191,7 +191,9 @@ TIMER: Optional[KernelTimer] = None
 # Test hook (tests/test_layers_gpu.py): called after every conv launch of the model path as
 # CHECK(kind, cs, **tensors) with kind in {"fwd", "dgrad", "wgrad"}, so a test can compare each
 # launch, at the exact shapes and data of a real step, with a torch fp32 reference of the
-# same op on the same (bf16) operands.  None in production.
+# same op on the same (bf16) operands.  None in production.  The BN passes report as "bn_fwd" /
+# "bn_bwd", the 3x3x3 convs of ops3d as "fwd3" / "bwd3" and its general convs as "fwdg" / "bwdg"
+# (tests/test_efe_gpu.py).
 CHECK = None
 
 

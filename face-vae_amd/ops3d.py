@@ -122,6 +122,8 @@ def conv3d_forward(cs: Conv3dState, x, bias, res=None, stats=False):
             part = torch.empty(nb * 2 * d.cout, dtype=F32, device=x.device)
             rec = (part, nb, bp)
     call("fv_conv3d_fwd", ctypes.byref(d), ptr(x), ptr(cs.wk), ptr(bias), ptr(res), ptr(y), ptr(part), stream())
+    if ops.CHECK is not None:
+        ops.CHECK("fwd3", cs, x=x, bias=bias, res=res, y=y)
     return y, rec
 
 
@@ -138,6 +140,8 @@ def conv3d_backward(cs: Conv3dState, x, dy, need_dx=True):
     if need_dx:
         dx = torch.empty((d.n, d.cin, d.d, d.h, d.w), dtype=dy.dtype, device=dev, memory_format=CL3)
         call("fv_conv3d_bwd_data", ctypes.byref(d), ptr(dy), ptr(cs.wt), ptr(dx), stream())
+    if ops.CHECK is not None:
+        ops.CHECK("bwd3", cs, x=x, dy=dy, dw=dw, db=db, dx=dx)
     return dx, dw, db
 
 
@@ -294,6 +298,8 @@ def conv3dg_forward(cs: Conv3dgState, x, bias):
         raise RuntimeError(f"conv3dg: input {tuple(x.shape)} {x.dtype} does not match its descriptor")
     y = torch.empty((d.n, d.cout, d.d, d.h, d.w), dtype=x.dtype, device=x.device, memory_format=CL3)
     call("fv_conv3dg_fwd", ctypes.byref(d), ptr(x), ptr(cs.wk), ptr(bias), ptr(y), stream())
+    if ops.CHECK is not None:
+        ops.CHECK("fwdg", cs, x=x, bias=bias, y=y)
     return y
 
 
@@ -315,6 +321,8 @@ def conv3dg_backward(cs: Conv3dgState, x, dy, need_dx=True, need_db=True):
             lo = torch.empty((d.n, d.cin, d.d, d.h // 2, d.w // 2), dtype=dy.dtype, device=dev, memory_format=CL3)
             call("fv_conv3dg_upsample_bwd", ctypes.byref(d), ptr(dx), ptr(lo), stream())
             dx = lo
+    if ops.CHECK is not None:
+        ops.CHECK("bwdg", cs, x=x, dy=dy, dw=dw, db=db, dx=dx)
     return dx, dw, db
 
 
@@ -391,6 +399,21 @@ class CNA3DFn(torch.autograd.Function):
         training = blk.training
         comm = blk.bn_comm()
         pbn = bn
+        cin_w = weight.shape[1]
+        cut_in = Cin == cin_w and Cin % 8 != 0
+        if cut_in:
+            # a channel count the conv kernels do not take (SameBlock3D(30, 15) on its own): pad on entry
+            xb = pad_channels(xb, ops.pad_pow2(Cin))
+            Cin = xb.shape[1]
+        if Cin != cin_w:
+            # the input carries zero pad channels (EFE_conv5.mix runs at pad_pow2(2K) channels): the
+            # weight gets zero columns for them
+            if Cin != ops.pad_pow2(cin_w):
+                raise RuntimeError(f"ConvBlock3D: input with {Cin} channels for a conv of {cin_w} "
+                                   f"({cin_w}, or {ops.pad_pow2(cin_w)} with a zero pad)")
+            wp = weight.new_zeros((cout, Cin) + tuple(weight.shape[2:]))
+            wp[:, :cin_w] = weight.detach()
+            weight = wp
         if cp != cout:
             weight, bias, pbn = _pad_rows(weight, cp), _pad_rows(bias, cp), _PaddedBN(bn, gamma, beta, cp)
         d = descg(dtype, N, D, H, W, Cin, cp, conv.kernel_size, blk.upsample)
@@ -404,6 +427,7 @@ class CNA3DFn(torch.autograd.Function):
             z = z[:, :cout].contiguous(memory_format=CL3)
         cs.release()
         ctx.blk, ctx.cs, ctx.r, ctx.comm, ctx.pbn, ctx.cout = blk, cs, r, comm, pbn, cout
+        ctx.cin_w, ctx.cut_in = cin_w, cut_in
         ctx.save_for_backward(x, xb, y)
         return z
 
@@ -421,6 +445,135 @@ class CNA3DFn(torch.autograd.Function):
             dz = full
         dy, dg, dbt = ops.bn_act_backward(as4d(dz), as4d(y), ctx.pbn, r, 0.0, blk.pool, ctx.comm)
         dx, dw, db = conv3dg_backward(cs, xb, as5d(dy, D), ctx.needs_input_grad[0])
+        if dx is not None and ctx.cut_in:
+            dx = dx[:, :ctx.cin_w].contiguous(memory_format=CL3)
         if dx is not None and dx.dtype != x.dtype:
             dx = dx.to(x.dtype)
+        if dw.shape[1] != ctx.cin_w:
+            dw = dw[:, :ctx.cin_w].contiguous()
         return dx, dw[:cout], db[:cout], dg[:cout], dbt[:cout], None
+
+
+class _PaddedConv3:
+    """Conv3d holder whose [C][C][3][3][3] weight and [C] bias are zero-padded to cp channels both
+    ways for this forward (what Conv3dState reads of a conv: `weight`, `out_channels`)."""
+
+    def __init__(self, weight, bias, cp):
+        c = weight.shape[0]
+        w = weight.new_zeros((cp, cp) + tuple(weight.shape[2:]))
+        w[:c, :c] = weight.detach()
+        self.weight, self.bias = w, _pad_rows(bias, cp)
+        self.in_channels = self.out_channels = cp
+
+
+class _PadState:
+    """The cp-channel images of a padded ResBlock3D's parameters and batch-norm buffers, kept per
+    block and device: the pad (zero weights and biases; gamma 1, beta 0, mean 0, var 1) is written
+    once, and a forward copies only the live [:C] parts in -- two strided copies for the conv weights
+    and one multi-tensor copy for the ten vectors -- instead of re-building every image with
+    zeros / cat (24 small launches per block and forward)."""
+
+    def __init__(self, blk, cp, device):
+        self.C, self.cp, self.device = blk.bn1.num_features, cp, device
+        self.convs = [_PaddedConv3(c.weight, c.bias, cp) for c in (blk.conv1, blk.conv2)]
+        self.bns = [_PaddedBN(bn, bn.weight, bn.bias, cp) for bn in (blk.bn1, blk.bn2)]
+
+    @staticmethod
+    def of(blk, cp, device):
+        st = blk.__dict__.get("_padstate")
+        if st is None or st.cp != cp or st.device != device:
+            st = _PadState(blk, cp, device)
+            blk.__dict__["_padstate"] = st
+        return st
+
+    def refresh(self, w1, b1, g1, be1, w2, b2, g2, be2):
+        C = self.C
+        with torch.no_grad():
+            self.convs[0].weight[:C, :C].copy_(w1)
+            self.convs[1].weight[:C, :C].copy_(w2)
+            dst, src = [self.convs[0].bias[:C], self.convs[1].bias[:C]], [b1, b2]
+            for pbn, g, be in ((self.bns[0], g1, be1), (self.bns[1], g2, be2)):
+                pbn.num_batches_tracked = pbn.bn.num_batches_tracked
+                dst += [pbn.weight[:C], pbn.bias[:C], pbn.running_mean[:C], pbn.running_var[:C]]
+                src += [g, be, pbn.bn.running_mean, pbn.bn.running_var]
+            torch._foreach_copy_(dst, [t.detach() for t in src])
+        return self.convs[0], self.convs[1], self.bns[0], self.bns[1]
+
+    def write_back(self):
+        C = self.C
+        with torch.no_grad():
+            torch._foreach_copy_([t for p in self.bns for t in (p.bn.running_mean, p.bn.running_var)],
+                                 [t[:C] for p in self.bns for t in (p.running_mean, p.running_var)])
+
+
+def pad_channels(x5, cp):
+    """NDHWC [N, C, D, H, W] -> NDHWC [N, cp, D, H, W] with zeros in channels [C, cp)."""
+    N, C, D, H, W = x5.shape
+    out = torch.empty((N, cp, D, H, W), dtype=x5.dtype, device=x5.device, memory_format=CL3).zero_()
+    out[:, :C] = x5
+    return out
+
+
+class ResBlock3DPadFn(torch.autograd.Function):
+    """ResBlock3D(C) for a C that is not 8 * 2^k, run at cp = pad_pow2(C) channels on the kernels of
+    ResBlock3DFn: weights and biases zero-padded per forward (_PaddedConv3), the two batch norms
+    through _PaddedBN, both kept in the block's _PadState.  The pad channels are zero on entry and stay exactly zero: batch norm maps 0
+    to 0 there (mean 0, shift 0), ReLU keeps it, the padded weight rows and biases are zero and so
+    is the residual.  x with C channels is padded on entry and the output cut on exit; x with cp
+    channels (pad zero: fv_efe_kpcat_fwd's output, or the previous block's) stays at cp channels,
+    with no copy either way, and so does its gradient."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, g1, be1, w2, b2, g2, be2, blk):
+        dtype = ops.storage(blk.compute_dtype())
+        C = blk.bn1.num_features
+        cp = ops.pad_pow2(C)
+        if x.shape[1] not in (C, cp):
+            raise RuntimeError(f"ResBlock3D({C}): input with {x.shape[1]} channels ({C}, or {cp} with a zero pad)")
+        cut = x.shape[1] == C
+        xb = to_ndhwc(x, dtype)
+        if cut:
+            xb = pad_channels(xb, cp)
+        N, _, D, H, W = xb.shape
+        training = blk.training
+        comm = blk.bn_comm()
+        ps = _PadState.of(blk, cp, x.device)
+        c1, c2, bn1, bn2 = ps.refresh(w1, b1, g1, be1, w2, b2, g2, be2)
+        d = desc3(dtype, N, D, H, W, cp, cp)
+        r1 = bn3d_stats(bn1, xb, None, training, comm)
+        a1 = as5d(ops.bn_act_forward(as4d(xb), r1, 0.0, False, bn1), D)
+        cs1 = Conv3dState(c1, d, x.device, True)
+        t1, rec = conv3d_forward(cs1, a1, c1.bias, stats=training)
+        r2 = bn3d_stats(bn2, t1, rec, training, comm)
+        a2 = as5d(ops.bn_act_forward(as4d(t1), r2, 0.0, False, bn2), D)
+        cs2 = Conv3dState(c2, d, x.device, True)
+        out, _ = conv3d_forward(cs2, a2, c2.bias, res=xb)
+        if training:
+            ps.write_back()
+        cs1.release()
+        cs2.release()
+        ctx.cs1, ctx.cs2, ctx.r1, ctx.r2, ctx.comm, ctx.bn1, ctx.bn2 = cs1, cs2, r1, r2, comm, bn1, bn2
+        ctx.C, ctx.cut, ctx.xdtype = C, cut, x.dtype
+        ctx.save_for_backward(xb, t1, a1, a2)
+        return out[:, :C].contiguous(memory_format=CL3) if cut else out
+
+    @staticmethod
+    def backward(ctx, dout):
+        xb, t1, a1, a2 = ctx.saved_tensors
+        cs1, cs2, r1, r2, comm, C = ctx.cs1, ctx.cs2, ctx.r1, ctx.r2, ctx.comm, ctx.C
+        D = xb.shape[2]
+        dout = to_ndhwc(dout, xb.dtype)
+        if ctx.cut:
+            dout = pad_channels(dout, xb.shape[1])
+        da2, dw2, db2 = conv3d_backward(cs2, a2, dout)
+        dt1, dg2, dbe2 = ops.bn_act_backward(as4d(da2), as4d(t1), ctx.bn2, r2, 0.0, False, comm)
+        da1, dw1, db1 = conv3d_backward(cs1, a1, as5d(dt1, D))
+        dxb, dg1, dbe1 = ops.bn_act_backward(as4d(da1), as4d(xb), ctx.bn1, r1, 0.0, False, comm,
+                                             addend=as4d(dout))
+        dx = as5d(dxb, D)
+        if ctx.cut:
+            dx = dx[:, :C].contiguous(memory_format=CL3)
+        if dx.dtype != ctx.xdtype:
+            dx = dx.to(ctx.xdtype)
+        return (dx, dw1[:C, :C].contiguous(), db1[:C], dg1[:C], dbe1[:C], dw2[:C, :C].contiguous(), db2[:C], dg2[:C],
+                dbe2[:C], None)

@@ -36,6 +36,9 @@
  *   fv_subsample2_*, fv_bn2_add_relu_fwd   ResBottleneck (modules.py:138-152): the stride of its
  *                            stride-2 1x1 convs and relu(down_sample(x) + layers(x)).
  *   fv_pose_pool_fwd, fv_pose_head_*   torch.mean, fc_*, softmax expectation (models.py:1025-1036).
+ *   fv_ckd_resize_fwd, fv_ckd_softargmax_*   CKD's F.interpolate (models.py:978) and
+ *                            heatmap2kp(out2heatmap(.)) (utils.py:106-118).
+ *   fv_efe_kpcat_*           EFE_conv5's torch.cat((x, kp2gaussian_3d(kpc)), 1) (models.py:790-791).
  *   fv_adam_step             torch.optim.Adam(lr, betas=(0.5,0.999)) (logger.py:60-61).
  *   fv_comm_*                distributed.py:24-31 init_process_group("nccl") + DDP's
  *                            gradient all-reduce (logger.py:55,58) + SyncBN collectives.
@@ -793,6 +796,27 @@ int fv_ckd_softargmax_fwd(int dtype, const void* z, int n, int k, int d, int h, 
                           float* stat, void* ws, void* stream);
 int fv_ckd_softargmax_bwd(int dtype, const void* z, const float* g_kp, const float* stat, int n, int k, int d, int h,
                           int w, float temperature, void* dz, void* stream);
+
+/* ---------------------------------------------- expression feature extractor pieces ---- */
+/* EFE_conv5 (models.py:724-799) between the conv / batch-norm entries above: the concatenation
+ * torch.cat((out_conv(x), kp2gaussian_3d(kpc, x.shape[2:])), 1) (models.py:790-791, utils.py:130-136).
+ * dtype FV_F32 or FV_BF16 storage, fp32 arithmetic, no float atomics, every cross-thread sum in a fixed
+ * order (reruns are bit-identical).  d, h, w >= 2; 1 <= k <= 256; cp must be the 2k channels padded
+ * to 8 * a power of two; d * h * w * cp < 2^31; anything else returns FV_E_UNSUPPORTED.
+ *
+ * fwd: z dense NDHWC [n][d * h * w][k] of `dtype` (rows of k elements, no alignment assumed), kpc
+ * [n][k][3] fp32 with (x, y, z) = (along W, along H, along D).  out [n][d * h * w][cp] of `dtype`:
+ * channels [0, k) are z bit for bit, channel k + i is exp(-0.5 |grid(v) - kpc[n][i]|^2 / kp_variance)
+ * on the grid 2 i / (size - 1) - 1, computed in fp32 and rounded once, channels [2k, cp) are zero.
+ * bwd: from g_out [n][d * h * w][cp], dz [n][d * h * w][k] = channels [0, k) of g_out (every element
+ * written) and dkpc[n][i][j] = sum_v g_out[n][v][k + i] G (grid_j(v) - kpc[n][i][j]) / kp_variance,
+ * G recomputed in fp32 from kpc, the sums carried in fp64.  ws: fv_efe_kpcat_ws_bytes (the per-chunk
+ * partials; 0 for unsupported arguments). */
+int fv_efe_kpcat_fwd(int dtype, const void* z, const float* kpc, int n, int k, int cp, int d, int h, int w,
+                     float kp_variance, void* out, void* stream);
+size_t fv_efe_kpcat_ws_bytes(int n, int k, int cp, int d, int h, int w);
+int fv_efe_kpcat_bwd(int dtype, const void* g_out, const float* kpc, int n, int k, int cp, int d, int h, int w,
+                     float kp_variance, void* dz, float* dkpc, void* ws, void* stream);
 
 #ifdef __cplusplus
 }
