@@ -1,6 +1,7 @@
 // Internal header of the 2-D convolution's translation units (conv.hip, conv_fwd.hip,
-// conv_fwd_v2.hip): the forward kernels' argument struct, the device helpers the kernel families
-// share, and the declarations of the host launchers of the families that have their own file.
+// conv_fwd_v2.hip, conv_wgrad.hip): the forward kernels' argument struct, the device helpers the
+// kernel families share, and the declarations of the forward families' host launchers (the
+// weight gradient's argument structs, plan types and launchers: conv_plan.h).
 // Kernels have internal linkage, so a kernel is launched only from its own file, through a
 // launcher.  Everything declared here that has linkage is hidden: the library exports the fv_*
 // entries only.
@@ -431,6 +432,30 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x4 (&acc)[RN
         }
       }
     }
+  }
+}
+
+template <int N>
+__device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+// wave-uniform count -> the matching immediate (counts above 15 wait for 15: stricter, safe)
+__device__ __forceinline__ void wait_vm_dyn(int n) {
+  switch (n) {
+    case 0: wait_vm<0>(); break;
+    case 1: wait_vm<1>(); break;
+    case 2: wait_vm<2>(); break;
+    case 3: wait_vm<3>(); break;
+    case 4: wait_vm<4>(); break;
+    case 5: wait_vm<5>(); break;
+    case 6: wait_vm<6>(); break;
+    case 7: wait_vm<7>(); break;
+    case 8: wait_vm<8>(); break;
+    case 9: wait_vm<9>(); break;
+    case 10: wait_vm<10>(); break;
+    case 11: wait_vm<11>(); break;
+    case 12: wait_vm<12>(); break;
+    case 13: wait_vm<13>(); break;
+    case 14: wait_vm<14>(); break;
+    default: wait_vm<15>(); break;
   }
 }
 
