@@ -275,7 +275,8 @@ conv3_halo_fwd2(ConvArgs a, unsigned x_bytes) {
   }
   FV_DIAG_LOOP_END();
   __syncthreads();
-  conv_epilogue<bf16, WN, WM, RN, RM, true>(a, acc, smem, co0, p0, tm, wn, wm, lane, tid);
+  // (whole-row tiles that cover the output exactly, halo_epi_ok: the epilogue's HALO form)
+  conv_epilogue<bf16, WN, WM, RN, RM, true, NoMid, false, true>(a, acc, smem, co0, p0, tm, wn, wm, lane, tid);
   FV_DIAG_END();
 }
 
@@ -661,12 +662,13 @@ conv3_halo_fwd3(ConvArgs a, unsigned x_bytes, int ntiles) {
       if constexpr (MODE == 1)
         subpix_epilogue<WM, RM>(a, acc, smem, cur.tn, cur.n, cur.th * TR, cur.tw * 64, cur.tm, wn, wm, lane, tid, mid);
       else
-        conv_epilogue<bf16, WN, WM, RN, RM, true>(a, acc, smem, cur.co0, cur.p0, cur.tm, wn, wm, lane, tid, mid);
+        conv_epilogue<bf16, WN, WM, RN, RM, true, decltype(mid), false, true>(a, acc, smem, cur.co0, cur.p0, cur.tm, wn, wm,
+                                                                              lane, tid, mid);
     } else {
       if constexpr (MODE == 1)
         subpix_epilogue<WM, RM>(a, acc, smem, cur.tn, cur.n, cur.th * TR, cur.tw * 64, cur.tm, wn, wm, lane, tid);
       else
-        conv_epilogue<bf16, WN, WM, RN, RM, true>(a, acc, smem, cur.co0, cur.p0, cur.tm, wn, wm, lane, tid);
+        conv_epilogue<bf16, WN, WM, RN, RM, true, NoMid, false, true>(a, acc, smem, cur.co0, cur.p0, cur.tm, wn, wm, lane, tid);
     }
     FV_DIAG_END();
     if (!nxt) break;
@@ -2618,6 +2620,14 @@ static int cu_count() {
   }
   return n;
 }
+// What conv_epilogue's HALO form (conv3_halo_fwd2 / fwd3 MODE 0 and 2) takes for granted, checked
+// next to every such launch: tiles of tr whole 64-pixel row segments and bn channels cover the
+// N x H x W x Cout output exactly and store to it in place (no sub-pixel phase, NHWC), so that
+// no stored element needs a bounds test (P % (tr * 64) == 0 and Cout % bn == 0 follow)
+static bool halo_epi_ok(const ConvArgs& a, int bn, int tr) {
+  return a.lgtw == 6 && !a.sub && !a.nchw && a.W % 64 == 0 && a.H % tr == 0 && a.P == a.N * a.H * a.W &&
+         a.ntn * bn == a.Cout && a.ldy >= a.Cout;
+}
 // one conv3_halo_fwd3 launch over ntiles tiles: schedule SCH 2 (stagger) unless FV_RES_SCHED
 // says 0 / 1 (-> 0), persistent (one block per CU) when there are more tiles than CUs
 template <int WN, int WM, int RN, int RM, int NSB, int MODE>
@@ -2826,6 +2836,11 @@ static int conv_run(const fv_conv_desc* d, const void* x, const void* wk, const 
     // registers (buffer_load_dwordx4 a step ahead, ds_write_b128 after the next barrier) instead
     // of LDS-DMA: res fwd / dgrad 147 / 136 -> 150.5 / 141 us, Generator.in_conv 147-152 ->
     // 160-162 us, step +0.17 ms.)
+    // the epilogue's HALO form tests no bounds: tiles of tr rows x 64 pixels x bn channels cover
+    // the output exactly (halo3_bn chose bn | cout for h % 4 == 0, w % 64 == 0)
+    const int tr = (bn == 64 && d->h % 8 == 0 && a.Cin % 64 == 0) ? 8 : 4;
+    FV_REQUIRE(halo_epi_ok(a, bn, tr), "halo 3x3 conv: %dx%d, cout %d is not whole tiles of %d rows x 64 px x %d co", d->h,
+               d->w, d->cout, tr, bn);
     if (bn >= 128 && a.Cin % 64 == 0) {
       if (bn == 256) launch_h3<4, 2, 4, 8, 2, 0>(nblk, s, a, xb);
       else launch_h3<2, 4, 4, 4, 3, 0>(nblk, s, a, xb);
@@ -2981,6 +2996,8 @@ int fv_conv2d_bwd_data(const fv_conv_desc* d, const void* dy, int ldy_dy, const 
     const int nblk = a.ntn * d->n * (a.H / 4) * (a.W / 64);
     const unsigned xb = (unsigned)((long)d->n * d->h * d->w * d->cout * 2);
     FV_REQUIRE((long)(a.Cin / 32) * 4 * a.wus / 2 <= phase_wt_elems(d), "low-res halo dgrad: weight image");
+    FV_REQUIRE(halo_epi_ok(a, bn, 4), "low-res halo dgrad: %dx%d, cin %d is not whole tiles of 4 rows x 64 px x %d co", a.H,
+               a.W, d->cin, bn);
     if (bn == 256) launch_h3<4, 2, 4, 8, 2, 2>(nblk, (hipStream_t)stream, a, xb);
     else launch_h3<2, 4, 4, 4, 3, 2>(nblk, (hipStream_t)stream, a, xb);
     return fv_check_launch("conv2d_bwd_data_lowres_halo");

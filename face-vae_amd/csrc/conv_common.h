@@ -150,6 +150,14 @@ __device__ __forceinline__ f32x4 mma(const Frag<float>& a, const Frag<float>& b,
   return c;
 }
 
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+// c + a * b with the product rounded before the add (never contracted to an FMA)
+__device__ __forceinline__ f32x2 mul_then_add(f32x2 a, f32x2 b, f32x2 c) {
+#pragma clang fp contract(off)
+  const f32x2 p = a * b;
+  return c + p;
+}
+
 // shared epilogue: bias [+ residual] -> BN partials -> [sigmoid] -> store (NHWC T or NCHW f32)
 // STAGED (bf16 NHWC only): after bias and BN partials the tile is rounded to bf16, written
 // to LDS (16-B chunks XOR-swizzled by pixel row) and stored with coalesced 16-B row
@@ -157,10 +165,18 @@ __device__ __forceinline__ f32x4 mma(const Frag<float>& a, const Frag<float>& b,
 // mid (persistent kernels): with a callable other than NoMid, every thread reads its store
 // chunks back into registers, the block syncs (LDS free again) and mid() runs -- it issues
 // the next tile's LDS-DMA prologue -- before the stores, which then drain under that DMA.
+// HALO (STAGED, the 3x3 halo kernels conv3_halo_fwd2 / fwd3): the block's pixels are whole
+// 64-pixel image rows (lgtw == 6), no sub-pixel phase, and the host checked that the tiles cover
+// the output exactly (halo_epi_ok: P % BM == 0, Cout % BN == 0).  Then no element needs a bounds
+// test, a thread's store-pass chunks are one per-lane byte offset (its chunk of tile row 0) from a
+// wave-uniform 64-bit base that advances by whole pixels / image rows, and the wave's RN * 16
+// bias values are one coalesced load, handed out by lane permutes.  Same operands, same order:
+// bit-identical to the general path.
 struct NoMid {
   __device__ void operator()() const {}
 };
-template <typename T, int WN, int WM, int RN, int RM, bool STAGED = false, typename Mid = NoMid, bool GSUB = false>
+template <typename T, int WN, int WM, int RN, int RM, bool STAGED = false, typename Mid = NoMid, bool GSUB = false,
+          bool HALO = false>
 __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x4 (&acc)[RN][RM], char* smem, int co0, int p0,
                                               int tm, int wn, int wm, int lane, int tid, Mid mid = Mid{}) {
   constexpr bool kMid = !std::is_same<Mid, NoMid>::value;
@@ -173,11 +189,51 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x4 (&acc)[RN
   // their HBM latency hides under the BN partials and the LDS staging (loaded inside the
   // store loop they were serialised behind its stores: +22 us per res conv at 64x64, B=32)
   constexpr int SCPR = BN / 8, NRES = STAGED ? (BM * SCPR + NT - 1) / NT : 1;
+  // HALO: a thread keeps its 16-B chunk column (NT % SCPR == 0) and moves PS tile pixels per
+  // store-pass iteration; PS divides the 64-pixel tile row, so iteration `it` is image row
+  // (it * PS) >> 6, column + (it * PS) & 63 of the tile for every thread
+  constexpr int PS = NT / SCPR;
+  static_assert(!HALO || (STAGED && !GSUB && RN * 16 == 64 && NT % SCPR == 0 && PS <= 64 && 64 % PS == 0 &&
+                          (BM * SCPR) % NT == 0),
+                "halo epilogue: tile geometry");
+  float hbias = 0.f;
+  if constexpr (HALO) {
+    // (first: the bias add is the epilogue's first consumer of a load)
+    if (a.bias) hbias = a.bias[co0 + wn * 64 + lane];
+  }
+  // (per-thread constants from an opaque copy of tid: as invariants of a persistent kernel's
+  // tile loop they would be hoisted out of it and held in registers through the main loop)
+  int htid = tid;
+  if constexpr (HALO) asm volatile("" : "+v"(htid));
+  const int hpl = htid / SCPR, hch = htid % SCPR;      // this thread's tile pixel (of PS) and chunk column
+  const unsigned hvo = HALO ? (unsigned)((hpl * a.ldy + hch * 8) * 2) : 0u;
+  const long hub = HALO ? ((long)p0 * a.ldy + co0) * 2 : 0L;
+  // address of this thread's chunk `it`: uniform base + uniform pixel step + per-lane offset
+  auto haddr = [&](const void* base, int it) -> char* {
+    const int pl = it * PS;
+    const char* ub = reinterpret_cast<const char*>(base) + hub + ((long)(pl >> 6) * a.W + (pl & 63)) * a.ldy * 2;
+    return const_cast<char*>(ub) + hvo;
+  };
+  // LDS byte offset of that chunk in the staged tile: pl = hpl + it * PS, and the bits it * PS
+  // adds to pl & (SCPR - 1) lie above hpl < PS, so they XOR into the swizzle as a constant; the
+  // iteration's offset it * PS * BN * 2 is an immediate below 64 KB from one of two bases
+  const int hsw = hch ^ (hpl & (SCPR - 1));
+  int hl[2] = {hpl * BN * 2, hpl * BN * 2 + 65536};
+  if constexpr (HALO && BM * BN * 2 > 65536) asm volatile("" : "+v"(hl[1]));
+  auto hlds = [&](int it) -> int {
+    constexpr int kRow = PS * BN * 2;
+    return (hl[(it * kRow) >> 16] | ((hsw ^ ((it * PS) & (SCPR - 1))) << 4)) + ((it * kRow) & 0xffff);
+  };
   uint4 rpre[NRES];
   // (with a mid hook the residual chunks are loaded after the LDS read-back instead, when the
   // accumulators are dead: their registers and the read-back's cannot all be live at once)
   auto load_res = [&]() {
-    if (a.res) {
+    if constexpr (HALO) {
+      if (a.res) {
+#pragma unroll
+        for (int it = 0; it < NRES; ++it) rpre[it] = *reinterpret_cast<const uint4*>(haddr(a.res, it));
+      }
+    } else if (a.res) {
 #pragma unroll
       for (int it = 0; it < NRES; ++it) {
         const int idx = tid + it * NT;
@@ -197,8 +253,13 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x4 (&acc)[RN
   for (int n = 0; n < RN; ++n)
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const int co = co0 + wn * RN * 16 + n * 16 + lh * 4 + i;
-      bv[n][i] = (a.bias && co < a.Cout) ? a.bias[co] : 0.f;
+      if constexpr (HALO) {
+        // lane l holds bias[wave's channel l]: this lane's 4 channels of tile n start at n * 16 + lh * 4
+        bv[n][i] = __int_as_float(__builtin_amdgcn_ds_bpermute((lh * 4 + n * 16 + i) << 2, __float_as_int(hbias)));
+      } else {
+        const int co = co0 + wn * RN * 16 + n * 16 + lh * 4 + i;
+        bv[n][i] = (a.bias && co < a.Cout) ? a.bias[co] : 0.f;
+      }
     }
   bool pv[RM];
   int pix_of[RM];
@@ -206,7 +267,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x4 (&acc)[RN
   for (int m = 0; m < RM; ++m) {
     const int loc = wm * RM * 16 + m * 16 + lr;
     const int tp = a.lgtw ? p0 + (loc >> a.lgtw) * a.W + (loc & ((1 << a.lgtw) - 1)) : p0 + loc;
-    pv[m] = tp < a.P;
+    pv[m] = HALO || tp < a.P;
     pix_of[m] = out_pix<GSUB>(a, tp);
   }
 #pragma unroll
@@ -263,7 +324,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x4 (&acc)[RN
       const float s01 = ii & 1 ? sv[1] : sv[0], s23 = ii & 1 ? sv[3] : sv[2];
       const float q01 = ii & 1 ? qv[1] : qv[0], q23 = ii & 1 ? qv[3] : qv[2];
       const float val = lr < 4 ? (ii & 2 ? s23 : s01) : (ii & 2 ? q23 : q01);
-      if (lr < 8 && cb + ii < a.Cout) a.stats[(long)(rec * 2 + (lr >> 2)) * a.Cout + cb + ii] = val;
+      if (lr < 8 && (HALO || cb + ii < a.Cout)) a.stats[(long)(rec * 2 + (lr >> 2)) * a.Cout + cb + ii] = val;
     }
   }
 
@@ -289,7 +350,8 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x4 (&acc)[RN
       for (int it = 0; it < NRES; ++it) {
         const int idx = tid + it * NT;
         const int pl = idx / CPR, ch = idx - (idx / CPR) * CPR;
-        if (idx < BM * CPR) vv[it] = *reinterpret_cast<const uint4*>(smem + pl * BN * 2 + ((ch ^ (pl & (CPR - 1))) << 4));
+        if constexpr (HALO) vv[it] = *reinterpret_cast<const uint4*>(smem + hlds(it));
+        else if (idx < BM * CPR) vv[it] = *reinterpret_cast<const uint4*>(smem + pl * BN * 2 + ((ch ^ (pl & (CPR - 1))) << 4));
       }
       __syncthreads();
       load_res();
@@ -297,8 +359,115 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x4 (&acc)[RN
     }
     auto chunk = [&](int it, int pl, int ch) -> uint4 {
       if constexpr (kMid) return vv[it];
+      else if constexpr (HALO) return *reinterpret_cast<const uint4*>(smem + hlds(it));
       else return *reinterpret_cast<const uint4*>(smem + pl * BN * 2 + ((ch ^ (pl & (CPR - 1))) << 4));
     };
+    if constexpr (HALO) {
+      // the store pass without bounds tests or per-chunk address arithmetic; its form -- residual
+      // added or not (ADD), records (REC = a.spm) -- is chosen once, not per chunk, so each form
+      // is one straight run of NRES chunks
+      static_assert(CPR <= 64 && 64 % CPR == 0, "store-pass records: chunks per row must divide a wave");
+      const int c = co0 + hch * 8;
+      // the sums as channel pairs (packed f32 adds / FMAs: no MFMA runs beside them here)
+      f32x2 sacc[4], qacc[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) sacc[k] = qacc[k] = f32x2{0.f, 0.f};
+      auto pass = [&](auto add, auto recs) {
+        constexpr bool ADD = decltype(add)::value;
+        constexpr int REC = decltype(recs)::value;
+        f32x2 bm_[4], bi_[4], bg_[4], bb_[4];
+        if constexpr (REC == 2) {
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            bm_[k] = f32x2{a.bnm[c + 2 * k], a.bnm[c + 2 * k + 1]};
+            bi_[k] = f32x2{a.bni[c + 2 * k], a.bni[c + 2 * k + 1]};
+            bg_[k] = f32x2{a.bng[c + 2 * k], a.bng[c + 2 * k + 1]};
+            bb_[k] = f32x2{a.bnb[c + 2 * k], a.bnb[c + 2 * k + 1]};
+          }
+        }
+#pragma unroll
+        for (int it = 0; it < NRES; ++it) {
+          Chunk8<bf16> v, r;
+          v.raw = chunk(it, 0, 0);
+          if constexpr (ADD || REC == 2) r.raw = rpre[it];
+          if constexpr (REC == 2) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+              const f32x2 rr = {r.get(2 * k), r.get(2 * k + 1)}, gv = {v.get(2 * k), v.get(2 * k + 1)};
+              const f32x2 yh = (rr - bm_[k]) * bi_[k];
+              const f32x2 t = bg_[k] * yh + bb_[k];
+              const f32x2 gs = gv * a.bns;
+              const f32x2 g = {t.x > 0.f ? gv.x : gs.x, t.y > 0.f ? gv.y : gs.y};
+              sacc[k] += g;
+              // sum of g * yhat: one FMA per term for channels 0-5 of the chunk, a rounded product
+              // and an add for channels 6, 7 -- the forms the general path's code compiles to,
+              // written out so that the records stay the same bit for bit
+              if (k < 3) qacc[k] = f32x2{__builtin_fmaf(g.x, yh.x, qacc[k].x), __builtin_fmaf(g.y, yh.y, qacc[k].y)};
+              else qacc[k] = mul_then_add(g, yh, qacc[k]);
+            }
+          } else {
+            if constexpr (ADD) {
+              float f[8];
+#pragma unroll
+              for (int j = 0; j < 8; ++j) f[j] = v.get(j) + r.get(j);
+              v.set8(f);
+            }
+            if constexpr (REC == 1) {
+              // (sums of the stored, bf16-rounded values)
+#pragma unroll
+              for (int k = 0; k < 4; ++k) {
+                const f32x2 o = {v.get(2 * k), v.get(2 * k + 1)};
+                sacc[k] += o;
+                qacc[k] += o * o;
+              }
+            }
+          }
+          v.store(reinterpret_cast<bf16*>(haddr(a.y, it)));
+          // (the chunks stay in order, each chunk's terms summed before the next: left free, the
+          // NRES bodies of this one block are interleaved and the terms kept for a late sum, until
+          // the 256-co tile and the persistent kernels spill)
+          if constexpr (REC != 0) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) asm volatile("" : "+v"(sacc[k]), "+v"(qacc[k]));
+          }
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      };
+      using No = std::false_type;
+      using Yes = std::true_type;
+      if (!a.spm) {
+        // the plain store pass (kept free of the record code: +2-3 us per res conv)
+        if (a.res) pass(Yes{}, std::integral_constant<int, 0>{});
+        else pass(No{}, std::integral_constant<int, 0>{});
+        return;
+      }
+      if (a.spm == 2) pass(No{}, std::integral_constant<int, 2>{});       // (res = the BN input, not added)
+      else if (a.res) pass(Yes{}, std::integral_constant<int, 1>{});
+      else pass(No{}, std::integral_constant<int, 1>{});
+      float ssum[8], qsum[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        ssum[j] = sacc[j >> 1][j & 1];
+        qsum[j] = qacc[j >> 1][j & 1];
+      }
+#pragma unroll
+      for (int o = CPR; o < 64; o <<= 1)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          ssum[j] += __shfl_xor(ssum[j], o, 64);
+          qsum[j] += __shfl_xor(qsum[j], o, 64);
+        }
+      if (lane < CPR) {
+        const long rec = (long)tm * (NT / 64) + (tid >> 6);
+        float* r0 = a.sprec + (rec * 2) * a.Cout + c;
+        float* r1 = a.sprec + (rec * 2 + 1) * a.Cout + c;
+        *reinterpret_cast<float4*>(r0) = make_float4(ssum[0], ssum[1], ssum[2], ssum[3]);
+        *reinterpret_cast<float4*>(r0 + 4) = make_float4(ssum[4], ssum[5], ssum[6], ssum[7]);
+        *reinterpret_cast<float4*>(r1) = make_float4(qsum[0], qsum[1], qsum[2], qsum[3]);
+        *reinterpret_cast<float4*>(r1 + 4) = make_float4(qsum[4], qsum[5], qsum[6], qsum[7]);
+      }
+      return;
+    }
     if (!a.spm) {
       // the plain store pass (kept free of the record code below: +2-3 us per res conv)
 #pragma unroll
