@@ -1,11 +1,35 @@
 // Internal header of the 2-D convolution's translation units, for what only they share (not
 // pose.hip or conv3d_gemm.hip, which include conv_common.h): the weight-gradient family's
-// argument structs, the plan types that conv.hip's planners fill, and every launcher of
-// conv_wgrad.hip.  Everything declared here that has linkage is hidden.
+// argument structs, the plan types that conv.hip's planners fill, the tile constants of the
+// special-shape kernels that the planners read, and every launcher of conv_halo3.hip,
+// conv_shapes.hip and conv_wgrad.hip.  Everything declared here that has linkage is hidden.
 #pragma once
 #include "conv_common.h"
 
 #pragma GCC visibility push(hidden)
+
+// ---- tile constants of conv_shapes.hip's kernels that conv.hip's planners and weight prep read ----
+constexpr int C74_TR = 4;     // conv7c4_fwd: output rows per tile (x 64 columns)
+constexpr int C74_K = 224;    // conv7c4_fwd: row length of the packed 7x7 weight image (7 x 32)
+constexpr int C64_G = 8;      // conv3c64_fwd: iterations (4 rows each) per BN record group
+constexpr int UPB_G = 4;      // conv3up_band_fwd: iterations (2 low-res rows each) per BN record group
+constexpr int C7_TR = 4;      // conv7_n3_fwd2: output rows per band step (H % C7_TR == 0)
+
+// ---- launchers of conv_halo3.hip: they pick the instantiation, the caller decides the rest.
+// Non-zero for a combination that is not instantiated. ----
+// conv3_halo_fwd3: bn = co tile (256 / 128 on 4 rows, 64 on 8 rows), mode 0 / 1 / 2 (bn 256), 0 / 2
+// (128), 0 (64), sch 0 / 2, pers only below bn 256; grid blocks over ntiles tiles
+int launch_halo3_fwd3(const ConvArgs& a, int bn, int mode, int sch, bool pers, int grid, unsigned xb, int ntiles,
+                      hipStream_t s);
+int launch_halo3_fwd2(const ConvArgs& a, int bn, int nblk, unsigned xb, hipStream_t s);   // bn 256 / 128 / 64
+
+// ---- launchers of conv_shapes.hip, one per kernel ----
+int launch_halo7(const ConvArgs& a, int cin, int nblk, unsigned xb, hipStream_t s);          // conv_halo_fwd, cin 8 / 64
+void launch_c74(const ConvArgs& a, int grid, unsigned xb, int ntiles, hipStream_t s);        // conv7c4_fwd
+void launch_c64(const ConvArgs& a, int nblk, unsigned xb, int nbands, hipStream_t s);        // conv3c64_fwd
+void launch_upband(const ConvArgs& a, int nblk, unsigned xb, int nbands, hipStream_t s);     // conv3up_band_fwd
+int launch_c1s(const ConvArgs& a, int k, int bpx, int grid, unsigned xb, hipStream_t s);     // conv1x1_stream<k, bpx>
+void launch_c7n(const ConvArgs& a, int nblk, unsigned xb, int band, hipStream_t s);          // conv7_n3_fwd2
 
 // ---- argument structs of the weight-gradient kernels (conv_wgrad.hip) ----
 struct WgArgs {

@@ -263,16 +263,13 @@ __device__ __forceinline__ bf16x8 tfrag(const char* base, int r0, int cbase, int
   return __builtin_bit_cast(bf16x8, v);
 }
 
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
 // ring wait: retire the oldest stage while `ahead` (0 .. NS-2, run-time) younger ones stay in flight
 template <int NS, int PW, int A = NS - 2>  // vmcnt immediate <= 63: (NS - 2) * PW must fit
 __device__ __forceinline__ void wait_ahead(int ahead) {
   if constexpr (A <= 0) {
-    wait_vmcnt<0>();
+    wait_vm<0>();
   } else {
-    if (ahead >= A) wait_vmcnt<A * PW>();
+    if (ahead >= A) wait_vm<A * PW>();
     else wait_ahead<NS, PW, A - 1>(ahead);
   }
 }

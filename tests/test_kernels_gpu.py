@@ -66,6 +66,7 @@ CONV_CASES = [
     (7, 64, 3, 8, 128, False, False),
     (7, 64, 3, 20, 64, False, False),   # out_conv wgrad: 3 ragged row segments
     (7, 64, 3, 64, 128, False, False),  # out_conv forward: a 64-row band per block (ring wraps 4x), below
+    (7, 5, 64, 4, 64, False, False),    # > 4 valid input channels: conv_halo_fwd<7, 8, ...>, not the packed conv7c4_fwd
     # halo-staged 3x3 (bf16, W % 64 == 0, H % 4 == 0): co tiles of 128 / 256 / 64, 2 column tiles
     (3, 64, 128, 8, 64, False, False),
     (3, 256, 256, 4, 64, False, False),
@@ -524,7 +525,7 @@ def test_up_wgrad_splits(spb, monkeypatch):
     assert rel(db, br.grad) < TOL[torch.bfloat16] * 1.5
 
 
-# 1x1 convs on the pixel-stream kernel (conv.hip conv1x1_stream): the mid convs' forward and
+# 1x1 convs on the pixel-stream kernel (conv_shapes.hip conv1x1_stream): the mid convs' forward and
 # data-gradient shapes -- one tile per stream, several tiles per stream (the t + 2 DMA under the
 # stores), 2 co groups -- bit-identical to conv_fwd_v2's 256 x 256 tile (same k order, same
 # epilogue: FV_C1S=0) and within bf16 tolerance of the torch fp32 conv
