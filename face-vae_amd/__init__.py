@@ -16,7 +16,8 @@ from .modules import (Conv2d, Conv3d, ConvBlock2D, ConvBlock3D, ConvTranspose2dE
                       MaxPool2d, ResBlock2D, ResBlock3D, ResBottleneck, SameBlock2D, SameBlock3D, UpBlock2D, UpBlock3D)
 from .optim import Adam
 from .pose import rotation_matrix_x, rotation_matrix_y, rotation_matrix_z, transform_kp
-from . import checkpoint, distributed, graph, ops, ops3d, ops_ckd, ops_efe, ops_pose, pose, warp
+from . import checkpoint, distributed, graph, ops, ops3d, ops_ckd, ops_efe, ops_pose, ops_tps, pose, warp
+from .transform import Transform
 from .graph import StepGraph
 
 __all__ = ["FaceVAEConfig", "compute_dtype", "set_compute_dtype", "KLDivergenceLoss", "L1Loss", "PerceptualLoss", "ReconLoss",
@@ -25,7 +26,8 @@ __all__ = ["FaceVAEConfig", "compute_dtype", "set_compute_dtype", "KLDivergenceL
            "MFE", "DownBlock3D", "UpBlock3D", "Conv3d", "HPE_EDE", "ResBottleneck", "MaxPool2d", "HeadPoseLoss",
            "transform_kp", "rotation_matrix_x", "rotation_matrix_y", "rotation_matrix_z", "ops_pose", "pose",
            "CKD", "EquivarianceLoss", "KeypointPriorLoss", "DeformationPriorLoss", "ops_ckd",
-           "EFE_conv5", "SameBlock3D", "ContrastiveLoss_linear", "ops_efe"]
+           "EFE_conv5", "SameBlock3D", "ContrastiveLoss_linear", "ops_efe",
+           "Transform", "ops_tps"]
 
 
 def __getattr__(name):

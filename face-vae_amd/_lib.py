@@ -261,6 +261,9 @@ _SIGS = {
     "fv_efe_kpcat_fwd": (c_int, [c_int, P, P] + [c_int] * 6 + [c_float, P, P]),
     "fv_efe_kpcat_ws_bytes": (c_size_t, [c_int] * 6),
     "fv_efe_kpcat_bwd": (c_int, [c_int, P, P] + [c_int] * 6 + [c_float, P, P, P, P]),
+    "fv_tps_warp_frame_fwd": (c_int, [P, P, P] + [c_int] * 5 + [P, P]),
+    "fv_tps_warp_coords_fwd": (c_int, [P, P, P] + [c_int] * 3 + [P, P]),
+    "fv_tps_warp_coords_bwd": (c_int, [P, P, P, P] + [c_int] * 3 + [P, P]),
 }
 
 _lib = None

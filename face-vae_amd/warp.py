@@ -3,6 +3,7 @@ warp.hip kernels.  No CPU fallback: every compute call goes through `_lib.call`.
 
 Reference functions mirrored (file:line in Luh1124/face-vae), same names and argument
 meaning, device-agnostic (the reference hard-codes .cuda(), utils.py:81-82, 93-95):
+  make_coordinate_grid_2d             utils.py:79-88
   make_coordinate_grid_3d             utils.py:91-103
   create_heatmap_representations      utils.py:130-137 (kp2gaussian_3d 123-129, variance 0.01)
   create_sparse_motions               utils.py:139-152
@@ -37,6 +38,16 @@ def _cuda(*ts):
 
 def _f32(t):
     return t.detach().float().contiguous() if t is not None else None
+
+
+def make_coordinate_grid_2d(spatial_size, device=None):
+    """[H, W, 2] grid of (x over W, y over H) in [-1, 1] (utils.py:79-88)."""
+    h, w = spatial_size
+    x = 2 * (torch.arange(h, device=device) / (h - 1)) - 1
+    y = 2 * (torch.arange(w, device=device) / (w - 1)) - 1
+    xx = x.view(-1, 1).repeat(1, w)
+    yy = y.view(1, -1).repeat(h, 1)
+    return torch.cat([yy.unsqueeze(2), xx.unsqueeze(2)], 2)
 
 
 def make_coordinate_grid_3d(spatial_size, device=None):

@@ -39,6 +39,8 @@
  *   fv_ckd_resize_fwd, fv_ckd_softargmax_*   CKD's F.interpolate (models.py:978) and
  *                            heatmap2kp(out2heatmap(.)) (utils.py:106-118).
  *   fv_efe_kpcat_*           EFE_conv5's torch.cat((x, kp2gaussian_3d(kpc)), 1) (models.py:790-791).
+ *   fv_tps_warp_*            Transform.transform_frame / warp_coordinates (trainer.py:106-129): the random
+ *                            affine + thin-plate-spline warp of the equivariance term.
  *   fv_adam_step             torch.optim.Adam(lr, betas=(0.5,0.999)) (logger.py:60-61).
  *   fv_comm_*                distributed.py:24-31 init_process_group("nccl") + DDP's
  *                            gradient all-reduce (logger.py:55,58) + SyncBN collectives.
@@ -817,6 +819,35 @@ int fv_efe_kpcat_fwd(int dtype, const void* z, const float* kpc, int n, int k, i
 size_t fv_efe_kpcat_ws_bytes(int n, int k, int cp, int d, int h, int w);
 int fv_efe_kpcat_bwd(int dtype, const void* g_out, const float* kpc, int n, int k, int cp, int d, int h, int w,
                      float kp_variance, void* dz, float* dkpc, void* ws, void* stream);
+
+/* ------------------------------------------------------ equivariance transform ---- */
+/* Transform (trainer.py:91-129; FOMM's random affine + thin-plate-spline warp).  For a point
+ * p = (x, y) of sample b:
+ *   T(p) = theta_b[:, :2] p + theta_b[:, 2] + r(p) (1, 1),  r(p) = sum_q c_{b,q} d_q^2 log(d_q + 1e-6),
+ *   d_q = |x - qx| + |y - qy| (L1, as the reference), q over the pts x pts control lattice
+ *   make_coordinate_grid_2d((pts, pts)) (utils.py:79-88): coordinate i is 2 (i / (pts - 1)) - 1 in
+ *   fp32, x fastest; the lattice is computed in the kernel.
+ * theta [n][2][3] and cparams [n][pts^2] are fp32 in DEVICE memory, read when the kernel runs.  fp32
+ * throughout, logf, the sum over q in ascending order, no atomics: reruns are bit-identical.  A point
+ * on a control point contributes 0 * log(1e-6) = 0.  2 <= pts <= 16; 1 <= n <= 65535; anything else
+ * returns FV_E_UNSUPPORTED.
+ *
+ * Frame (transform_frame, trainer.py:106-110): y[n][c][i][j] = F.grid_sample(x, T(grid),
+ * align_corners=True, padding_mode="reflection") with grid(i, j) = (2 (j / (w - 1)) - 1,
+ * 2 (i / (h - 1)) - 1), bilinear, in ATen's arithmetic: ((g + 1) / 2) (size - 1), reflected about 0 and
+ * size - 1 (fabs, fmod by the span, parity of the flip count), clipped to [0, size - 1], floor, four
+ * corners, a corner outside the image contributing 0.  x and y dense NCHW fp32 [n][c][h][w]; h, w >= 2;
+ * c >= 1; h * w < 2^31 - 256.  There is no backward: the frame is data (trainer.py:271-272).
+ * Coordinates (warp_coordinates, trainer.py:112-129): out[n][m][:] = T(coords[n][m][:]), [n][m][2] fp32,
+ * m >= 1.  bwd, in the coordinates only (theta and cparams are constants):
+ *   g_coords = theta[:, :2]^T g_out + (g_out.x + g_out.y) grad r,
+ *   dr/dx = sum_q c_q (2 d_q log(d_q + 1e-6) + d_q^2 / (d_q + 1e-6)) sign(x - qx), sign(0) = 0. */
+int fv_tps_warp_frame_fwd(const float* x, const float* theta, const float* cparams, int n, int c, int h, int w, int pts,
+                          float* y, void* stream);
+int fv_tps_warp_coords_fwd(const float* coords, const float* theta, const float* cparams, int n, int m, int pts, float* out,
+                           void* stream);
+int fv_tps_warp_coords_bwd(const float* coords, const float* g_out, const float* theta, const float* cparams, int n, int m,
+                           int pts, float* g_coords, void* stream);
 
 #ifdef __cplusplus
 }
