@@ -40,6 +40,11 @@ class Conv3dgDesc(ctypes.Structure):
                 ("cin", c_int), ("cout", c_int), ("ksize", c_int), ("upsample", c_int)]
 
 
+class PwDesc(ctypes.Structure):
+    _fields_ = [("dtype", c_int), ("n", c_int), ("h", c_int), ("w", c_int), ("stride", c_int),
+                ("cin", c_int), ("cout", c_int), ("in_relu", c_int), ("out_relu", c_int)]
+
+
 class StoreReduce(ctypes.Structure):
     _fields_ = [("mode", c_int), ("records", c_void_p), ("bn_input", c_void_p), ("mean", c_void_p),
                 ("invstd", c_void_p), ("gamma", c_void_p), ("beta", c_void_p), ("slope", c_float)]
@@ -59,6 +64,7 @@ P = c_void_p
 D = POINTER(ConvDesc)
 D3 = POINTER(Conv3dDesc)
 D3G = POINTER(Conv3dgDesc)
+DPW = POINTER(PwDesc)
 # name -> (restype, argtypes)
 _SIGS = {
     "fv_abi_version": (c_int, []),
@@ -264,6 +270,10 @@ _SIGS = {
     "fv_tps_warp_frame_fwd": (c_int, [P, P, P] + [c_int] * 5 + [P, P]),
     "fv_tps_warp_coords_fwd": (c_int, [P, P, P] + [c_int] * 3 + [P, P]),
     "fv_tps_warp_coords_bwd": (c_int, [P, P, P, P] + [c_int] * 3 + [P, P]),
+    "fv_hopenet_prep_fwd": (c_int, [P] + [c_int] * 5 + [POINTER(c_float), POINTER(c_float), P, P]),
+    "fv_pw_infer_wk_elems": (c_size_t, [DPW]),
+    "fv_pw_infer_weight_prep": (c_int, [DPW, P, P, P, P]),
+    "fv_pw_infer_fwd": (c_int, [DPW, P, P, P, P, P, P]),
 }
 
 _lib = None

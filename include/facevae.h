@@ -41,6 +41,8 @@
  *   fv_efe_kpcat_*           EFE_conv5's torch.cat((x, kp2gaussian_3d(kpc)), 1) (models.py:790-791).
  *   fv_tps_warp_*            Transform.transform_frame / warp_coordinates (trainer.py:106-129): the random
  *                            affine + thin-plate-spline warp of the equivariance term.
+ *   fv_hopenet_prep_fwd, fv_pw_infer_*   the frozen Hopenet teacher (trainer.py:16-88, 278-280): ImageNet
+ *                            normalisation + nearest resize, and its 1x1 convs with the batch norm folded in.
  *   fv_adam_step             torch.optim.Adam(lr, betas=(0.5,0.999)) (logger.py:60-61).
  *   fv_comm_*                distributed.py:24-31 init_process_group("nccl") + DDP's
  *                            gradient all-reduce (logger.py:55,58) + SyncBN collectives.
@@ -848,6 +850,46 @@ int fv_tps_warp_coords_fwd(const float* coords, const float* theta, const float*
                            void* stream);
 int fv_tps_warp_coords_bwd(const float* coords, const float* g_out, const float* theta, const float* cparams, int n, int m,
                            int pts, float* g_coords, void* stream);
+
+/* ------------------------------------------------------ frozen Hopenet teacher pieces ---- */
+/* The inference path of the frozen Hopenet teacher (trainer.py:16-88, called at trainer.py:278-280)
+ * beyond the stem, pool, 3x3 conv and pose-head entries above.  Inference only: no entry here has
+ * a gradient, nothing is saved, no BN records are written.  No float atomics, every sum in a fixed
+ * order: reruns are bit-identical.
+ *
+ * Preprocessing: y = F.interpolate((x - mean[c]) / std[c], size=(ho, wo)) (nearest; utils.py:182-186
+ * and trainer.py:280) in one launch, bit-equal to torch on the CPU: fp32 subtraction, IEEE division,
+ * and ATen's legacy nearest source index min((int)floorf(dst * scale), in - 1) with
+ * scale = (float)in / (float)out in fp32.  x NCHW fp32 [n][3][h][w], y NCHW fp32 [n][3][ho][wo] (what
+ * fv_stem7s2_fwd reads); mean and std are HOST arrays of 3 floats, read by the call.
+ * 1 <= n <= 65535, every size >= 1, h * w and ho * wo < 2^31 - 256; else FV_E_UNSUPPORTED. */
+int fv_hopenet_prep_fwd(const float* x, int n, int h, int w, int ho, int wo, const float* mean, const float* std, float* y,
+                        void* stream);
+/* Pointwise (1x1) convolution of a frozen network on the matrix units (FV_BF16: bf16 MFMA with fp32
+ * accumulation; FV_F32: the exact fp32 MFMA), with the batch norm folded into the weights and a
+ * per-channel shift, the stride folded into the pixel addressing and the ReLUs and the residual add
+ * into the load and the store:
+ *   y[p][co] = out_act(sum_ci in_act(x[src(p)][ci]) (w[co][ci] scale[co]) + shift[co] + res[p][co])
+ * x dense NHWC [n][h][w][cin], y and res dense NHWC [n][h / stride][w / stride][cout], all of `dtype`;
+ * src(p) is input pixel (stride i, stride j) of output pixel (i, j).  wk [cout][cin] of `dtype`
+ * (fv_pw_infer_wk_elems) is written by weight_prep from the parameter w [cout][cin] (fp32) and scale
+ * [cout] (NULL: 1): the product is formed in fp32 and rounded once.  shift [cout] fp32 and res may be
+ * NULL.  The accumulator, shift and residual are added in fp32 and rounded once at the store.  The
+ * pixel count needs no padding: short and partial tiles are predicated.  y aliasing x or res:
+ * FV_E_BADARG.  cin / cout not multiples of 32 in [32, 4096], stride outside {1, 2}, odd h or w at
+ * stride 2, n < 1, n * h * w >= 2^31 - 256: FV_E_UNSUPPORTED (wk_elems returns 0). */
+typedef struct fv_pw_desc {
+  int dtype;            /* FV_F32 or FV_BF16 */
+  int n, h, w;          /* INPUT size, dense NHWC with `cin` channels */
+  int stride;           /* 1, or 2: output (h/2, w/2) takes input pixel (2i, 2j); h, w even */
+  int cin, cout;        /* multiples of 32 in [32, 4096] */
+  int in_relu;          /* 1: the conv reads max(x, 0) */
+  int out_relu;         /* 1: y = max(., 0) */
+} fv_pw_desc;
+size_t fv_pw_infer_wk_elems(const fv_pw_desc* d);
+int fv_pw_infer_weight_prep(const fv_pw_desc* d, const float* w, const float* scale, void* wk, void* stream);
+int fv_pw_infer_fwd(const fv_pw_desc* d, const void* x, const void* wk, const float* shift, const void* res, void* y,
+                    void* stream);
 
 #ifdef __cplusplus
 }
