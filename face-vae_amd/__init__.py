@@ -15,10 +15,11 @@ from .models import AFE, CKD, EFE_conv5, HPE_EDE, MFE, Discriminator, FaceVAE, G
 from .modules import (Conv2d, Conv3d, ConvBlock2D, ConvBlock3D, ConvTranspose2dELR, DownBlock2D, DownBlock3D,
                       MaxPool2d, ResBlock2D, ResBlock3D, ResBottleneck, SameBlock2D, SameBlock3D, UpBlock2D, UpBlock3D)
 from .optim import Adam
-from .pose import rotation_matrix_x, rotation_matrix_y, rotation_matrix_z, transform_kp
-from . import checkpoint, distributed, graph, ops, ops3d, ops_ckd, ops_efe, ops_hopenet, ops_pose, ops_tps, pose, warp
+from .pose import rotation_matrix_x, rotation_matrix_y, rotation_matrix_z, transform_kp, transform_kp_with_new_pose
+from . import animate, checkpoint, distributed, graph, ops, ops3d, ops_ckd, ops_efe, ops_hopenet, ops_pose, ops_tps, pose, warp
 from .transform import Transform
 from .hopenet import Hopenet
+from .animate import Animator
 from .graph import StepGraph
 
 __all__ = ["FaceVAEConfig", "compute_dtype", "set_compute_dtype", "KLDivergenceLoss", "L1Loss", "PerceptualLoss", "ReconLoss",
@@ -28,7 +29,8 @@ __all__ = ["FaceVAEConfig", "compute_dtype", "set_compute_dtype", "KLDivergenceL
            "transform_kp", "rotation_matrix_x", "rotation_matrix_y", "rotation_matrix_z", "ops_pose", "pose",
            "CKD", "EquivarianceLoss", "KeypointPriorLoss", "DeformationPriorLoss", "ops_ckd",
            "EFE_conv5", "SameBlock3D", "ContrastiveLoss_linear", "ops_efe",
-           "Transform", "ops_tps", "Hopenet", "ops_hopenet"]
+           "Transform", "ops_tps", "Hopenet", "ops_hopenet",
+           "Animator", "animate", "transform_kp_with_new_pose"]
 
 
 def __getattr__(name):

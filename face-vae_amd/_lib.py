@@ -274,6 +274,9 @@ _SIGS = {
     "fv_pw_infer_wk_elems": (c_size_t, [DPW]),
     "fv_pw_infer_weight_prep": (c_int, [DPW, P, P, P, P]),
     "fv_pw_infer_fwd": (c_int, [DPW, P, P, P, P, P, P]),
+    "fv_mfe_input_fwd": (c_int, [c_int, P, P, P, P] + [c_int] * 7 + [c_float, P, P]),
+    "fv_motion_warp_fwd": (c_int, [c_int, P, P, P, P, P] + [c_int] * 7 + [P, P, P, P]),
+    "fv_frames_u8": (c_int, [P, P, c_int, c_int, c_int, P, P]),
 }
 
 _lib = None

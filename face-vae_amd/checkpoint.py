@@ -71,6 +71,29 @@ def load_reference_checkpoint(path: str, afe: Optional[AFE] = None, generator: O
     return out
 
 
+def load_reference_models(path: str, names=("afe", "ckd", "hpe_ede", "mfe", "generator"), efe: bool = False,
+                          map_location="cpu") -> Dict[str, torch.nn.Module]:
+    """Load the generator-side entries `names` (and `"efe"` when asked) of a reference Logger
+    checkpoint strictly into default-constructed modules -- what evaluate.py:14-20 does -- and
+    return them by name, on the CPU, in the mode they were constructed in.  Raises KeyError on a
+    missing entry or a differing key, ValueError on a differing shape."""
+    from . import models
+    ctors = {"afe": models.AFE, "ckd": models.CKD, "hpe_ede": models.HPE_EDE, "mfe": models.MFE,
+             "generator": models.Generator, "efe": models.EFE_conv5}
+    names = tuple(names) + (("efe",) if efe and "efe" not in names else ())
+    unknown = [n for n in names if n not in ctors]
+    if unknown:
+        raise KeyError(f"load_reference_models: unknown model names {unknown} (known: {sorted(ctors)})")
+    ckp = torch.load(path, map_location=map_location, weights_only=True)
+    out = {}
+    for name in names:
+        if name not in ckp:
+            raise KeyError(f"{path}: no {name!r} entry (keys: {sorted(ckp)[:8]})")
+        out[name] = ctors[name]()
+        _strict_load(out[name], ckp[name], name)
+    return out
+
+
 def save_reference_checkpoint(path: str, afe: AFE, generator: Generator, optimizers: Optional[Dict] = None,
                               epoch: int = 0):
     """Write afe / generator (+ their Adam states) in Logger.save_cpk's layout."""

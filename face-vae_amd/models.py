@@ -115,6 +115,33 @@ class MFE(_Block):
         occlusion = self.occlusion_conv(ops3d.depth_merge(x, mode), sigmoid=True)   # models.py:1080-1081
         return deformation, occlusion, mask
 
+    def infer(self, fs, kp_s, kp_d, Rs, Rd, fc=None, J=None):
+        """Inference-only forward up to the mask logits: the hourglass input comes from one fused
+        launch (warp.mfe_input), so no sparse-motion, heat-map or per-motion sample tensor is written.
+        -> (x [N, C, D, H, W] the hourglass features that mask_conv and the occlusion conv read,
+        mask_logits [N, K+1, D, H, W], fc = compress(fs)).  Pass the returned fc back in to skip the
+        compress of an unchanged source (fs may then be None).  The source side (fs / fc, kp_s, Rs) is
+        a batch of 1 or of kp_d's N.  The blend of the logits is Generator.infer's (warp.motion_warp).
+        J = warp.motion_jacobian(Rs, Rd) may be passed when the caller has formed it.  Eval mode only; runs under torch.no_grad() and raises on an input that requires grad."""
+        if self.training:
+            raise RuntimeError("facevae_amd MFE.infer is inference-only: call .eval() first (batch statistics are "
+                               "not collected on this path)")
+        ts = (fs, kp_s, kp_d, Rs, Rd, fc, J)
+        if fs is None and fc is None:
+            raise ValueError("facevae_amd MFE.infer: the appearance volume fs or its compressed form fc is required")
+        if any(t is not None and not t.is_cuda for t in ts):
+            raise RuntimeError("facevae_amd ops run on the GPU only (HIP); got a CPU tensor")
+        warp._no_grad_inputs("MFE.infer", *ts)
+        dtype = ops.storage(self.compute_dtype())
+        with torch.no_grad():
+            _batched_weight_prep(self, kp_d.device)
+            if fc is None:
+                fc = self.compress(fs)
+            inp = warp.mfe_input(fc, kp_s, kp_d, Rs, Rd, dtype, J=J)
+            out = self.up(self.down(inp))
+            x = torch.cat([inp, out], dim=1).contiguous(memory_format=ops3d.CL3)   # models.py:1074
+            return x, self.mask_conv(x), fc
+
 
 class HPE_EDE(_Block):
     """Head pose estimator (models.py:990-1037): a ResNet-50-shaped trunk -- `pre_layers` (7x7
@@ -447,6 +474,25 @@ class Generator(_Block):
         elif deformation is not None:
             raise ValueError("Generator: a deformation needs the 5-D feature volume fs [N, C, D, H, W]")
         return self.forward_2d(fs, occlusion)
+
+    def infer(self, fs, mask_logits, kp_s, kp_d, Rs, Rd, occlusion, J=None):
+        """Inference-only forward from the MFE's mask logits: the softmax, the blend of the K+1
+        motions and the warp of fs [1 or N, C, D, H, W] are one fused launch (warp.motion_warp; no
+        sparse-motion tensor, no separate grid sample), then the depth merge and forward_2d as in
+        forward.  -> (image [N, 3, H, W] fp32, deformation [N, D, H, W, 3] fp32).  J as in MFE.infer.
+        Eval mode only (no
+        power iteration); runs under torch.no_grad() and raises on an input that requires grad."""
+        if self.training:
+            raise RuntimeError("facevae_amd Generator.infer is inference-only: call .eval() first")
+        ts = (fs, mask_logits, kp_s, kp_d, Rs, Rd, occlusion, J)
+        if any(t is not None and not t.is_cuda for t in ts):
+            raise RuntimeError("facevae_amd ops run on the GPU only (HIP); got a CPU tensor")
+        warp._no_grad_inputs("Generator.infer", *ts)
+        mode = self.compute_dtype()
+        with torch.no_grad():
+            _batched_weight_prep(self, fs.device)
+            warped, deformation, _ = warp.motion_warp(mask_logits, fs, kp_s, kp_d, Rs, Rd, ops.storage(mode), J=J)
+            return self.forward_2d(ops3d.depth_merge(warped, mode), occlusion), deformation
 
 
 class Discriminator(_Block):

@@ -36,3 +36,20 @@ def transform_kp(canonical_kp, yaw, pitch, roll, t, scale):
     rot_mat = rotation_matrix_y(pitch) @ rotation_matrix_x(yaw) @ rotation_matrix_z(roll)
     kp = torch.matmul(rot_mat.unsqueeze(1), scale * canonical_kp.unsqueeze(-1)).squeeze(-1) + t.unsqueeze(1)
     return kp, rot_mat
+
+
+def transform_kp_with_new_pose(canonical_kp, yaw, pitch, roll, t, delta, new_yaw, new_pitch, new_roll):
+    """utils.py:62-76: the keypoints under another head pose.  R_new = Ry(new_pitch) @ Rx(new_yaw) @
+    Rz(new_roll); kp = R_new canonical_kp + t + (R_new inv(R_old)) delta, with delta [N, K, 3] the
+    expression offset estimated under the old pose (yaw, pitch, roll); then ONE z-shift for the
+    whole batch, 0.33 - mean(kp[..., 2]) over every sample and keypoint.  canonical_kp takes no scale
+    here (the caller multiplies it in).  -> (kp [N, K, 3], R_new [N, 3, 3])."""
+    old_rot_mat = rotation_matrix_y(pitch) @ rotation_matrix_x(yaw) @ rotation_matrix_z(roll)
+    rot_mat = rotation_matrix_y(new_pitch) @ rotation_matrix_x(new_yaw) @ rotation_matrix_z(new_roll)
+    R = torch.matmul(rot_mat, torch.inverse(old_rot_mat))
+    kp = (torch.matmul(rot_mat.unsqueeze(1), canonical_kp.unsqueeze(-1)).squeeze(-1) + t.unsqueeze(1)
+          + torch.matmul(R.unsqueeze(1), delta.unsqueeze(-1)).squeeze(-1))
+    zt = 0.33 - kp[:, :, 2].mean()
+    shift = torch.zeros(3, dtype=kp.dtype, device=kp.device)
+    shift[2] = zt
+    return kp + shift, rot_mat

@@ -12,6 +12,11 @@ meaning, device-agnostic (the reference hard-codes .cuda(), utils.py:81-82, 93-9
   grid_sample_3d                      F.grid_sample(..., align_corners=True) for 5-D inputs
                                       (models.py:1103, utils.py:175): trilinear, zeros padding
   occlusion_multiply                  fs * occlusion (models.py:1106)
+Inference only (csrc/animate.hip; no backward, an input that requires grad raises):
+  mfe_input                           the MFE's hourglass input in one launch (models.py:1066-1071)
+  motion_warp                         mask softmax + blend of the K+1 motions + grid_sample of fs in one
+                                      launch (models.py:1076-1078, 1103)
+  frames_u8                           evaluate.py:39-44: cat(dim=3), clip(0, 1), (255 * a).astype(uint8)
 The 5-D feature volumes are NDHWC (torch.channels_last_3d); motion fields / grids stay fp32
 [N, ..., 3] as the reference's.  grid_sample's input gradient is a bucketed gather (output
 voxels counting-sorted by base input cell, each bucket then ordered by voxel index, each input
@@ -258,3 +263,89 @@ def deformation_from_mask(mask_logits, sparse_motion):
     [N, K+1, D, H, W, 1])."""
     deform, prob = MotionMaskFn.apply(mask_logits, sparse_motion)
     return deform, prob.unsqueeze(-1)
+
+
+# ----------------------------------------------------------------------------------------
+# inference-only fused motion path (animate.hip): no backward, nothing saved
+# ----------------------------------------------------------------------------------------
+
+def _no_grad_inputs(name, *ts):
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts):
+        raise RuntimeError(f"{name} is inference-only (no backward): call it under torch.no_grad() or detach its "
+                           "inputs; it will not silently cut a graph")
+
+
+def _ndhwc(t, dtype):
+    return t if t.dtype == dtype and t.is_contiguous(memory_format=CL3) else t.to(dtype).contiguous(memory_format=CL3)
+
+
+def motion_jacobian(Rs, Rd):
+    """J = Rs inv(Rd) [N, 3, 3] of create_sparse_motions (utils.py:146), for callers that run both
+    fused launches on one pose pair and form it once (torch.inverse is a solver call)."""
+    return torch.matmul(Rs, torch.inverse(Rd))
+
+
+def _motion_args(name, kp_s, kp_d, Rs, Rd, Ns, J):
+    N, K, _ = kp_d.shape
+    if Ns not in (1, N) or kp_s.shape[0] != Ns or kp_s.shape[1] != K or Rs.shape[0] not in (1, N) or Rd.shape[0] != N:
+        raise RuntimeError(f"{name}: a source batch of 1 or N = {N} (volume, kp_s, Rs), kp_d / Rd of N; got volume "
+                           f"{Ns}, kp_s {tuple(kp_s.shape)}, Rs {tuple(Rs.shape)}, Rd {tuple(Rd.shape)}")
+    if J is None:
+        J = motion_jacobian(Rs, Rd)
+    elif J.dim() != 3 or J.shape[0] not in (1, N) or tuple(J.shape[1:]) != (3, 3):
+        raise RuntimeError(f"{name}: J must be [1 or {N}, 3, 3], got {tuple(J.shape)}")
+    return N, K, _f32(kp_s), _f32(kp_d), _f32(J.expand(N, 3, 3))
+
+
+def mfe_input(fc, kp_s, kp_d, Rs, Rd, dtype, kp_variance=0.01, J=None):
+    """The MFE's hourglass input (models.py:1066-1071) in one launch: [N, (K+1)(C2+1), D, H, W] NDHWC
+    of `dtype`, channel k (C2+1) the heat value and the next C2 the compressed volume fc
+    [Ns, C2, D, H, W] sampled at motion k -- what create_heatmap_representations,
+    create_sparse_motions, create_deformed_source_image and the cat build, without writing any of
+    them.  Ns is 1 or N: one source volume (and kp_s, Rs) serves every driving sample.  J = Rs inv(Rd)
+    is formed here unless the caller passes it (motion_jacobian).  Inference only."""
+    _cuda(fc, kp_s, kp_d, Rs, Rd, J)
+    _no_grad_inputs("mfe_input", fc, kp_s, kp_d, Rs, Rd, J)
+    Ns, C2, D, H, W = fc.shape
+    N, K, ks, kd, j = _motion_args("mfe_input", kp_s, kp_d, Rs, Rd, Ns, J)
+    fb = _ndhwc(fc.detach(), dtype)
+    out = torch.empty((N, (K + 1) * (C2 + 1), D, H, W), dtype=dtype, device=fc.device, memory_format=CL3)
+    call("fv_mfe_input_fwd", L.dtype_code(dtype), ptr(fb), ptr(ks), ptr(kd), ptr(j), N, Ns, K, C2, D, H, W,
+         float(kp_variance), ptr(out), stream())
+    return out
+
+
+def motion_warp(mask_logits, fs, kp_s, kp_d, Rs, Rd, dtype, need_mask=False, J=None):
+    """Mask blend and warp (models.py:1076-1078, 1103) in one launch: softmax of mask_logits
+    [N, K+1, D, H, W] over K+1, deformation = sum_k p_k motion_k with the motions recomputed from the
+    keypoints, and fs [Ns, C, D, H, W] sampled there.  -> (warped [N, C, D, H, W] NDHWC of `dtype`
+    = grid_sample_3d's output, deformation [N, D, H, W, 3] fp32, mask [N, K+1, D, H, W, 1] fp32 or
+    None).  The logits are read in the NDHWC layout mask_conv writes.  J as in mfe_input.
+    Inference only."""
+    _cuda(mask_logits, fs, kp_s, kp_d, Rs, Rd, J)
+    _no_grad_inputs("motion_warp", mask_logits, fs, kp_s, kp_d, Rs, Rd, J)
+    Ns, C, D, H, W = fs.shape
+    N, K, ks, kd, j = _motion_args("motion_warp", kp_s, kp_d, Rs, Rd, Ns, J)
+    if tuple(mask_logits.shape) != (N, K + 1, D, H, W):
+        raise RuntimeError(f"motion_warp: mask_logits {tuple(mask_logits.shape)}, expected {(N, K + 1, D, H, W)}")
+    lg, fb = _ndhwc(mask_logits.detach(), dtype), _ndhwc(fs.detach(), dtype)
+    out = torch.empty((N, C, D, H, W), dtype=dtype, device=fs.device, memory_format=CL3)
+    deform = torch.empty((N, D, H, W, 3), dtype=F32, device=fs.device)
+    prob = torch.empty((N, K + 1, D, H, W), dtype=F32, device=fs.device) if need_mask else None
+    call("fv_motion_warp_fwd", L.dtype_code(dtype), ptr(lg), ptr(fb), ptr(ks), ptr(kd), ptr(j), N, Ns, K, C, D, H, W,
+         ptr(out), ptr(deform), ptr(prob), stream())
+    return out, deform, prob.unsqueeze(-1) if need_mask else None
+
+
+def frames_u8(driving, generated):
+    """[N, H, 2W, 3] uint8, driving left and generated right, byte = trunc(255 * clip(x, 0, 1))
+    (evaluate.py:39-44), from two [N, 3, H, W] fp32 NCHW tensors."""
+    _cuda(driving, generated)
+    if driving.shape != generated.shape or driving.dim() != 4 or driving.shape[1] != 3:
+        raise RuntimeError(f"frames_u8: two [N, 3, H, W] tensors, got {tuple(driving.shape)} and "
+                           f"{tuple(generated.shape)}")
+    N, _, H, W = driving.shape
+    d32, g32 = _f32(driving), _f32(generated)
+    out = torch.empty((N, H, 2 * W, 3), dtype=torch.uint8, device=driving.device)
+    call("fv_frames_u8", ptr(d32), ptr(g32), N, H, W, ptr(out), stream())
+    return out

@@ -43,6 +43,8 @@
  *                            affine + thin-plate-spline warp of the equivariance term.
  *   fv_hopenet_prep_fwd, fv_pw_infer_*   the frozen Hopenet teacher (trainer.py:16-88, 278-280): ImageNet
  *                            normalisation + nearest resize, and its 1x1 convs with the batch norm folded in.
+ *   fv_mfe_input_fwd, fv_motion_warp_fwd, fv_frames_u8   the inference data flow of evaluate.py: the
+ *                            MFE's hourglass input, mask blend + warp, and the uint8 frame output.
  *   fv_adam_step             torch.optim.Adam(lr, betas=(0.5,0.999)) (logger.py:60-61).
  *   fv_comm_*                distributed.py:24-31 init_process_group("nccl") + DDP's
  *                            gradient all-reduce (logger.py:55,58) + SyncBN collectives.
@@ -890,6 +892,34 @@ size_t fv_pw_infer_wk_elems(const fv_pw_desc* d);
 int fv_pw_infer_weight_prep(const fv_pw_desc* d, const float* w, const float* scale, void* wk, void* stream);
 int fv_pw_infer_fwd(const fv_pw_desc* d, const void* x, const void* wk, const float* shift, const void* res, void* y,
                     void* stream);
+
+/* --------------------------------------------------- reenactment inference (Animator) ---- */
+/* Inference only: no gradient, nothing saved, no atomics (reruns are bit-identical).  Shared
+ * arguments: kp_s [Ns][K][3], kp_d [N][K][3], J [N][3][3] (= Rs inv(Rd)), all fp32; Ns is 1 or N,
+ * and with Ns == 1 every driving sample reads source 0 (volume and kp_s).  Volumes are dense NDHWC of
+ * `dtype` (FV_F32 or FV_BF16).  Motion k of a voxel is the identity grid point id for k = 0 and
+ * J (id - kp_d[k-1]) + kp_s[k-1] otherwise; sampling is trilinear, zeros padding, align_corners=True.
+ * D, H, W >= 2; one lane per (voxel, motion) resp. (voxel, 8 channels), and the lane count N D H W (K+1)
+ * resp. N D H W C / 8 must stay below 2^31 - 256.
+ *
+ * The MFE's hourglass input (models.py:1066-1071) in one launch, without the sparse-motion, heat-map
+ * and per-motion sample tensors: out [N][D][H][W][(K+1)(C2+1)], channel k (C2+1) = the heat value (0 for
+ * k = 0, else G(kp_d[k-1]) - G(kp_s[k-1]), G(kp) = exp(-|id - kp|^2 / (2 var))), channels
+ * k (C2+1) + 1 + c = fc [Ns][D][H][W][C2] sampled at motion k.  C2 + 1 <= 16; out 16-byte aligned. */
+int fv_mfe_input_fwd(int dtype, const void* fc, const float* kp_s, const float* kp_d, const float* J, int N, int Ns,
+                     int K, int C2, int D, int H, int W, float var, void* out, void* stream);
+/* Mask blend and warp (models.py:1076-1078, 1103) in one launch: per voxel the softmax over the K + 1
+ * logits (logits [N][D][H][W][K+1] of `dtype`, the layout mask_conv writes), deformation = sum_k p_k
+ * motion_k with the motions recomputed, and fs [Ns][D][H][W][C] sampled there.  out [N][D][H][W][C] of
+ * `dtype`, deformation [N][D][H][W][3] fp32, prob [N][K+1][D][H][W] fp32 or NULL (the other two
+ * outputs do not depend on it).  C a multiple of 8. */
+int fv_motion_warp_fwd(int dtype, const void* logits, const void* fs, const float* kp_s, const float* kp_d,
+                       const float* J, int N, int Ns, int K, int C, int D, int H, int W, void* out, float* deformation,
+                       float* prob, void* stream);
+/* Side-by-side frames (evaluate.py:39-44): driving and generated [N][3][H][W] fp32 NCHW ->
+ * out [N][H][2W][3] uint8, driving left; byte = trunc(255.0f * min(max(x, 0), 1)), one fp32 multiply
+ * and a truncation, bit-equal to numpy's clip(0, 1) and (255 * a).astype(uint8).  out 4-byte aligned. */
+int fv_frames_u8(const float* driving, const float* generated, int N, int H, int W, void* out, void* stream);
 
 #ifdef __cplusplus
 }
