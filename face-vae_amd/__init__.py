@@ -19,7 +19,7 @@ from .pose import rotation_matrix_x, rotation_matrix_y, rotation_matrix_z, trans
 from . import animate, checkpoint, distributed, graph, ops, ops3d, ops_ckd, ops_efe, ops_hopenet, ops_pose, ops_tps, pose, warp
 from .transform import Transform
 from .hopenet import Hopenet
-from .animate import Animator
+from .animate import Animator, CapturedDrive
 from .graph import StepGraph
 
 __all__ = ["FaceVAEConfig", "compute_dtype", "set_compute_dtype", "KLDivergenceLoss", "L1Loss", "PerceptualLoss", "ReconLoss",
@@ -30,7 +30,7 @@ __all__ = ["FaceVAEConfig", "compute_dtype", "set_compute_dtype", "KLDivergenceL
            "CKD", "EquivarianceLoss", "KeypointPriorLoss", "DeformationPriorLoss", "ops_ckd",
            "EFE_conv5", "SameBlock3D", "ContrastiveLoss_linear", "ops_efe",
            "Transform", "ops_tps", "Hopenet", "ops_hopenet",
-           "Animator", "animate", "transform_kp_with_new_pose"]
+           "Animator", "CapturedDrive", "animate", "transform_kp_with_new_pose"]
 
 
 def __getattr__(name):

@@ -277,6 +277,9 @@ _SIGS = {
     "fv_mfe_input_fwd": (c_int, [c_int, P, P, P, P] + [c_int] * 7 + [c_float, P, P]),
     "fv_motion_warp_fwd": (c_int, [c_int, P, P, P, P, P] + [c_int] * 7 + [P, P, P, P]),
     "fv_frames_u8": (c_int, [P, P, c_int, c_int, c_int, P, P]),
+    "fv_frames_from_u8": (c_int, [P, c_int, c_int, c_int, P, P]),
+    "fv_pose_kp_fwd": (c_int, [P] * 7 + [c_int] * 4 + [P, P, P, P]),
+    "fv_pose_kp_new_fwd": (c_int, [P] * 10 + [c_int] * 3 + [P, P, P, P]),
 }
 
 _lib = None

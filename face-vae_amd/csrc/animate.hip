@@ -9,6 +9,8 @@
 //   mask softmax, deformation sum           models.py:1076-1078
 //   F.grid_sample(fs, deformation)          models.py:1103
 //   cat(dim=3), clip(0, 1), (255 * a).astype(uint8)   evaluate.py:39-44
+//   img_as_float32 of the uint8 frames       dataset.py (skimage): x * fp32(1 / 255)
+//   transform_kp, transform_kp_with_new_pose, Rs inv(Rd)   utils.py:53-76, 146
 #include "common.h"
 
 namespace {
@@ -264,6 +266,160 @@ __global__ void __launch_bounds__(256) frames_u8(const float* __restrict__ drv, 
   }
 }
 
+// ---- fv_frames_from_u8 -----------------------------------------------------------------------
+// in [T][H][W][3] uint8 -> out [T][3][H][W] fp32 = x * fp32(1 / 255): one rounded multiply, as numpy's
+// np.multiply(a, float32(1 / 255), dtype=float32).  One lane per 4 input bytes (one 32-bit load when the
+// input is 4-byte aligned); byte b of the input is channel b % 3 of pixel b / 3.
+__device__ __forceinline__ void frame_float(float* __restrict__ out, unsigned byte, long b, long HW) {
+  const int c = (int)(b % 3);
+  const long p = b / 3;               // pixel index over [T][H][W]
+  const long n = p / HW;
+  out[(n * 3 + c) * HW + (p - n * HW)] = __fmul_rn((float)byte, (float)(1.0 / 255.0));
+}
+
+template <bool ALIGNED>
+__global__ void __launch_bounds__(256) frames_from_u8(const uint8_t* __restrict__ in, float* __restrict__ out,
+                                                      long nbytes, long HW) {
+  const long b0 = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
+  if (b0 >= nbytes) return;
+  if (ALIGNED && b0 + 4 <= nbytes) {
+    const unsigned word = *reinterpret_cast<const unsigned*>(in + b0);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) frame_float(out, (word >> (8 * i)) & 0xffu, b0 + i, HW);
+  } else {
+    const long b1 = b0 + 4 < nbytes ? b0 + 4 : nbytes;
+    for (long b = b0; b < b1; ++b) frame_float(out, in[b], b, HW);
+  }
+}
+
+// ---- fv_pose_kp_fwd / fv_pose_kp_new_fwd -------------------------------------------------------
+// transform_kp / transform_kp_with_new_pose (utils.py:53-76) and the motion Jacobian Rs inv(R) of
+// create_sparse_motions (utils.py:146).  A few hundred keypoints at most: latency, not bandwidth.  Every
+// lane rebuilds its sample's 3x3 matrices from the angles (sinf / cosf); nothing is exchanged but the
+// z-sum of the new-pose kernel.
+struct Mat3 {
+  float m[9];
+};
+
+__device__ __forceinline__ Mat3 mul3(const Mat3& a, const Mat3& b) {
+  Mat3 r;
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+      r.m[i * 3 + j] = a.m[i * 3] * b.m[j] + a.m[i * 3 + 1] * b.m[3 + j] + a.m[i * 3 + 2] * b.m[6 + j];
+  return r;
+}
+
+// Ry(pitch) Rx(yaw) Rz(roll) in the reference's naming of the axes (utils.py:5-57)
+__device__ __forceinline__ Mat3 rotation(float yaw, float pitch, float roll) {
+  const float cy = cosf(yaw), sy = sinf(yaw), cp = cosf(pitch), sp = sinf(pitch), cr = cosf(roll), sr = sinf(roll);
+  const Mat3 rx = {{cy, 0.f, sy, 0.f, 1.f, 0.f, -sy, 0.f, cy}};
+  const Mat3 ry = {{1.f, 0.f, 0.f, 0.f, cp, -sp, 0.f, sp, cp}};
+  const Mat3 rz = {{cr, -sr, 0.f, sr, cr, 0.f, 0.f, 0.f, 1.f}};
+  return mul3(mul3(ry, rx), rz);
+}
+
+// the general inverse (adjugate over determinant), as torch.inverse: not the transpose
+__device__ __forceinline__ Mat3 inverse3(const Mat3& a) {
+  const float* m = a.m;
+  const float c00 = m[4] * m[8] - m[5] * m[7], c01 = m[5] * m[6] - m[3] * m[8], c02 = m[3] * m[7] - m[4] * m[6];
+  const float id = 1.f / (m[0] * c00 + m[1] * c01 + m[2] * c02);
+  Mat3 r;
+  r.m[0] = c00 * id;
+  r.m[1] = (m[2] * m[7] - m[1] * m[8]) * id;
+  r.m[2] = (m[1] * m[5] - m[2] * m[4]) * id;
+  r.m[3] = c01 * id;
+  r.m[4] = (m[0] * m[8] - m[2] * m[6]) * id;
+  r.m[5] = (m[2] * m[3] - m[0] * m[5]) * id;
+  r.m[6] = c02 * id;
+  r.m[7] = (m[1] * m[6] - m[0] * m[7]) * id;
+  r.m[8] = (m[0] * m[4] - m[1] * m[3]) * id;
+  return r;
+}
+
+__device__ __forceinline__ void apply3(const Mat3& a, float x, float y, float z, float* o) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i) o[i] = a.m[i * 3] * x + a.m[i * 3 + 1] * y + a.m[i * 3 + 2] * z;
+}
+
+// lane 0 of a sample: R and, for a non-null Rs, J = Rs inv(R)
+__device__ __forceinline__ void store_R_J(const Mat3& R, const float* __restrict__ Rs, int ns, float* __restrict__ Rout,
+                                          float* __restrict__ J, int n) {
+#pragma unroll
+  for (int i = 0; i < 9; ++i) Rout[(long)n * 9 + i] = R.m[i];
+  if (Rs) {
+    Mat3 s;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) s.m[i] = Rs[(long)ns * 9 + i];
+    const Mat3 j = mul3(s, inverse3(R));
+#pragma unroll
+    for (int i = 0; i < 9; ++i) J[(long)n * 9 + i] = j.m[i];
+  }
+}
+
+// one lane per (sample, keypoint)
+__global__ void __launch_bounds__(256) pose_kp_fwd(const float* __restrict__ kp_c, const float* __restrict__ yaw,
+                                                   const float* __restrict__ pitch, const float* __restrict__ roll,
+                                                   const float* __restrict__ t, const float* __restrict__ scale,
+                                                   const float* __restrict__ Rs, float* __restrict__ kp,
+                                                   float* __restrict__ Rout, float* __restrict__ J, int N, int Nc, int Ns,
+                                                   int K) {
+  const int gid = blockIdx.x * 256 + threadIdx.x;
+  if (gid >= N * K) return;
+  const int n = gid / K, k = gid - n * K;
+  const Mat3 R = rotation(yaw[n], pitch[n], roll[n]);
+  const float* c = kp_c + ((long)(Nc == 1 ? 0 : n) * K + k) * 3;
+  const float s = scale[n];
+  float o[3];
+  apply3(R, s * c[0], s * c[1], s * c[2], o);
+#pragma unroll
+  for (int i = 0; i < 3; ++i) kp[(long)gid * 3 + i] = o[i] + t[n * 3 + i];
+  if (k == 0) store_R_J(R, Rs, Ns == 1 ? 0 : n, Rout, J, n);
+}
+
+// One block.  Lane l owns keypoints l, l + 256, ...: it writes their unshifted coordinates, sums its z in
+// that order, the 256 partial sums are added by one fixed tree in LDS, and every lane then shifts the z it
+// wrote itself.  The order of the sum depends on N K alone.
+constexpr int PN_THREADS = 256;
+constexpr int PN_MAX_KP = 1 << 16;   // 256 keypoints per lane: keeps the single block's loop short
+
+__global__ void __launch_bounds__(PN_THREADS) pose_kp_new_fwd(
+    const float* __restrict__ kp_in, const float* __restrict__ yaw, const float* __restrict__ pitch,
+    const float* __restrict__ roll, const float* __restrict__ t, const float* __restrict__ delta,
+    const float* __restrict__ nyaw, const float* __restrict__ npitch, const float* __restrict__ nroll,
+    const float* __restrict__ Rs, float* __restrict__ kp, float* __restrict__ Rout, float* __restrict__ J, int N,
+    int Ns, int K) {
+  __shared__ float part[PN_THREADS];
+  const int total = N * K;
+  float zsum = 0.f;
+  for (int g = threadIdx.x; g < total; g += PN_THREADS) {
+    const int n = g / K, k = g - n * K;
+    const Mat3 Rn = rotation(nyaw[n], npitch[n], nroll[n]);
+    const Mat3 Rrel = mul3(Rn, inverse3(rotation(yaw[n], pitch[n], roll[n])));
+    const float* c = kp_in + (long)g * 3;
+    const float* d = delta + (long)g * 3;
+    float a[3], b[3];
+    apply3(Rn, c[0], c[1], c[2], a);
+    apply3(Rrel, d[0], d[1], d[2], b);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) a[i] = a[i] + t[n * 3 + i] + b[i];
+    kp[(long)g * 3] = a[0];
+    kp[(long)g * 3 + 1] = a[1];
+    kp[(long)g * 3 + 2] = a[2];
+    zsum += a[2];
+    if (k == 0) store_R_J(Rn, Rs, Ns == 1 ? 0 : n, Rout, J, n);
+  }
+  part[threadIdx.x] = zsum;
+  __syncthreads();
+  for (int s = PN_THREADS / 2; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) part[threadIdx.x] += part[threadIdx.x + s];
+    __syncthreads();
+  }
+  const float shift = 0.33f - part[0] / (float)total;
+  for (int g = threadIdx.x; g < total; g += PN_THREADS) kp[(long)g * 3 + 2] += shift;
+}
+
 bool motion_args_ok(const void* a, const void* b, const float* kp_s, const float* kp_d, const float* J, int N, int Ns,
                     int K, int D, int H, int W) {
   return a && b && kp_s && kp_d && J && N > 0 && (Ns == 1 || Ns == N) && K > 0 && D > 1 && H > 1 && W > 1;
@@ -331,6 +487,46 @@ int fv_frames_u8(const float* driving, const float* generated, int N, int H, int
   hipLaunchKernelGGL(frames_u8, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, driving, generated,
                      (uint8_t*)out, nbytes, H, W);
   return fv_check_launch("frames_u8");
+}
+
+int fv_frames_from_u8(const void* frames, int T, int H, int W, float* out, void* stream) {
+  FV_REQUIRE(frames && out && T > 0 && H > 0 && W > 0, "frames_from_u8: bad argument");
+  const long HW = (long)H * W, nbytes = (long)T * HW * 3;
+  const long nblk = ((nbytes + 3) / 4 + 255) / 256;
+  FV_REQUIRE(nblk < (1L << 31), "frames_from_u8: too many pixels");
+  const dim3 grid((unsigned)nblk);
+  hipStream_t s = (hipStream_t)stream;
+  if (((uintptr_t)frames & 3) == 0)
+    hipLaunchKernelGGL(frames_from_u8<true>, grid, dim3(256), 0, s, (const uint8_t*)frames, out, nbytes, HW);
+  else
+    hipLaunchKernelGGL(frames_from_u8<false>, grid, dim3(256), 0, s, (const uint8_t*)frames, out, nbytes, HW);
+  return fv_check_launch("frames_from_u8");
+}
+
+int fv_pose_kp_fwd(const float* kp_c, const float* yaw, const float* pitch, const float* roll, const float* t,
+                   const float* scale, const float* Rs, int N, int Nc, int Ns, int K, float* kp, float* R, float* J,
+                   void* stream) {
+  FV_REQUIRE(kp_c && yaw && pitch && roll && t && scale && kp && R && N > 0 && K > 0, "pose_kp: bad argument");
+  FV_REQUIRE(Nc == 1 || Nc == N, "pose_kp: kp_c holds 1 or N = %d samples (got %d)", N, Nc);
+  FV_REQUIRE(!Rs || (J && (Ns == 1 || Ns == N)), "pose_kp: Rs needs J and 1 or N = %d samples (got %d)", N, Ns);
+  FV_REQUIRE((long)N * K < (1L << 31) - 256, "pose_kp: N K must stay below 2^31 - 256");
+  hipLaunchKernelGGL(pose_kp_fwd, dim3((unsigned)((N * K + 255) / 256)), dim3(256), 0, (hipStream_t)stream, kp_c, yaw,
+                     pitch, roll, t, scale, Rs, kp, R, J, N, Nc, Ns, K);
+  return fv_check_launch("pose_kp_fwd");
+}
+
+int fv_pose_kp_new_fwd(const float* kp_in, const float* yaw, const float* pitch, const float* roll, const float* t,
+                       const float* delta, const float* new_yaw, const float* new_pitch, const float* new_roll,
+                       const float* Rs, int N, int Ns, int K, float* kp, float* R, float* J, void* stream) {
+  FV_REQUIRE(kp_in && yaw && pitch && roll && t && delta && new_yaw && new_pitch && new_roll && kp && R && N > 0 &&
+                 K > 0, "pose_kp_new: bad argument");
+  FV_REQUIRE(!Rs || (J && (Ns == 1 || Ns == N)), "pose_kp_new: Rs needs J and 1 or N = %d samples (got %d)", N, Ns);
+  FV_REQUIRE((long)N * K <= PN_MAX_KP,
+             "pose_kp_new: N K <= %d (got %ld): the z-mean over the call is one block's fixed-order sum", PN_MAX_KP,
+             (long)N * K);
+  hipLaunchKernelGGL(pose_kp_new_fwd, dim3(1), dim3(PN_THREADS), 0, (hipStream_t)stream, kp_in, yaw, pitch, roll, t,
+                     delta, new_yaw, new_pitch, new_roll, Rs, kp, R, J, N, Ns, K);
+  return fv_check_launch("pose_kp_new_fwd");
 }
 
 }  // extern "C"

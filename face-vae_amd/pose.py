@@ -1,10 +1,15 @@
 """Head pose -> keypoints (utils.py:5-59 of Luh1124/face-vae): the three axis rotations and
 `transform_kp`, which turns canonical keypoints and the HPE_EDE outputs into the posed keypoints
 and the rotation matrix the MFE takes (kp_s / kp_d, Rs / Rd).  A handful of [N, 3, 3] and
-[N, K, 3] tensors: plain torch ops, on whatever device the inputs live."""
+[N, K, 3] tensors: plain torch ops, on whatever device the inputs live.  `pose_kp` / `pose_kp_new` are
+the inference-only one-launch forms of the two transforms (GPU only), which also return the motion
+Jacobian Rs inv(R)."""
 from __future__ import annotations
 
 import torch
+
+from . import warp
+from ._lib import call, ptr, stream
 
 
 def _rot(theta, rows):
@@ -53,3 +58,63 @@ def transform_kp_with_new_pose(canonical_kp, yaw, pitch, roll, t, delta, new_yaw
     shift = torch.zeros(3, dtype=kp.dtype, device=kp.device)
     shift[2] = zt
     return kp + shift, rot_mat
+
+
+# ----------------------------------------------------------------------------------------
+# inference-only fused forms (csrc/animate.hip): one launch each, no solver call, no host
+# synchronisation, so they can sit inside a HIP-graph capture (animate.CapturedDrive)
+# ----------------------------------------------------------------------------------------
+
+def _fused_args(name, N, Rs, *ts):
+    warp._cuda(*ts, Rs)
+    warp._no_grad_inputs(name, *ts, Rs)
+    if Rs is not None and (Rs.dim() != 3 or Rs.shape[0] not in (1, N) or tuple(Rs.shape[1:]) != (3, 3)):
+        raise ValueError(f"{name}: Rs must be [1 or {N}, 3, 3], got {list(Rs.shape)}")
+    return [warp._f32(x) for x in ts], warp._f32(Rs)
+
+
+def _angles(name, N, **angles):
+    for k, a in angles.items():
+        if a.numel() != N:
+            raise ValueError(f"{name}: {k} must hold {N} angles, got {list(a.shape)}")
+
+
+def pose_kp(kp_c, yaw, pitch, roll, t, scale, Rs=None):
+    """transform_kp and the motion Jacobian in one launch (fv_pose_kp_fwd).  kp_c [1 or N, K, 3];
+    yaw / pitch / roll [N]; t [N, 3]; scale [N] in any shape (HPE_EDE's [N, 1, 1, 1]); Rs [1 or N, 3, 3]
+    or None.  -> (kp [N, K, 3], R [N, 3, 3], J = Rs inv(R) [N, 3, 3] or None), fp32.  GPU and inference
+    only."""
+    N = yaw.numel()
+    (c, y, p, r, tt, s), rs = _fused_args("pose_kp", N, Rs, kp_c, yaw, pitch, roll, t, scale)
+    _angles("pose_kp", N, pitch=p, roll=r, scale=s)
+    if c.dim() != 3 or c.shape[0] not in (1, N) or c.shape[2] != 3 or tuple(tt.shape) != (N, 3):
+        raise ValueError(f"pose_kp: kp_c [1 or {N}, K, 3] and t [{N}, 3], got {list(c.shape)} and {list(tt.shape)}")
+    K = c.shape[1]
+    kp = torch.empty((N, K, 3), dtype=torch.float32, device=c.device)
+    R = torch.empty((N, 3, 3), dtype=torch.float32, device=c.device)
+    J = torch.empty_like(R) if rs is not None else None
+    call("fv_pose_kp_fwd", ptr(c), ptr(y), ptr(p), ptr(r), ptr(tt), ptr(s), ptr(rs), N, c.shape[0],
+         rs.shape[0] if rs is not None else 0, K, ptr(kp), ptr(R), ptr(J), stream())
+    return kp, R, J
+
+
+def pose_kp_new(kp_in, yaw, pitch, roll, t, delta, new_yaw, new_pitch, new_roll, Rs=None):
+    """transform_kp_with_new_pose and the motion Jacobian in one launch (fv_pose_kp_new_fwd).  kp_in
+    (the caller's scale * kp_c) and delta [N, K, 3]; the six angle tensors [N]; t [N, 3].  -> (kp
+    [N, K, 3] after the z-shift 0.33 - mean(z) over all N K keypoints of the call, R_new [N, 3, 3],
+    J = Rs inv(R_new) or None), fp32.  The mean is one block's fixed-order sum, so N K <= 65536.  GPU
+    and inference only."""
+    N = yaw.numel()
+    (c, y, p, r, tt, d, ny, np_, nr), rs = _fused_args("pose_kp_new", N, Rs, kp_in, yaw, pitch, roll, t, delta,
+                                                        new_yaw, new_pitch, new_roll)
+    _angles("pose_kp_new", N, pitch=p, roll=r, new_yaw=ny, new_pitch=np_, new_roll=nr)
+    if c.dim() != 3 or c.shape[0] != N or c.shape[2] != 3 or d.shape != c.shape or tuple(tt.shape) != (N, 3):
+        raise ValueError(f"pose_kp_new: kp_in and delta [{N}, K, 3] and t [{N}, 3], got {list(c.shape)}, "
+                         f"{list(d.shape)} and {list(tt.shape)}")
+    K = c.shape[1]
+    kp = torch.empty((N, K, 3), dtype=torch.float32, device=c.device)
+    R = torch.empty((N, 3, 3), dtype=torch.float32, device=c.device)
+    J = torch.empty_like(R) if rs is not None else None
+    call("fv_pose_kp_new_fwd", ptr(c), ptr(y), ptr(p), ptr(r), ptr(tt), ptr(d), ptr(ny), ptr(np_), ptr(nr), ptr(rs),
+         N, rs.shape[0] if rs is not None else 0, K, ptr(kp), ptr(R), ptr(J), stream())
+    return kp, R, J

@@ -349,3 +349,17 @@ def frames_u8(driving, generated):
     out = torch.empty((N, H, 2 * W, 3), dtype=torch.uint8, device=driving.device)
     call("fv_frames_u8", ptr(d32), ptr(g32), N, H, W, ptr(out), stream())
     return out
+
+
+def frames_from_u8(frames_u8):
+    """The way in, the inverse layout of frames_u8: [T, H, W, 3] uint8 -> [T, 3, H, W] fp32 NCHW,
+    x * fp32(1 / 255) in one rounded multiply -- bit-equal to data.u8_to_float (img_as_float32)."""
+    _cuda(frames_u8)
+    if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[3] != 3:
+        raise RuntimeError(f"frames_from_u8: a [T, H, W, 3] uint8 tensor, got {tuple(frames_u8.shape)} "
+                           f"{frames_u8.dtype}")
+    T, H, W, _ = frames_u8.shape
+    src = frames_u8.contiguous()
+    out = torch.empty((T, 3, H, W), dtype=F32, device=src.device)
+    call("fv_frames_from_u8", ptr(src), T, H, W, ptr(out), stream())
+    return out

@@ -45,6 +45,8 @@
  *                            normalisation + nearest resize, and its 1x1 convs with the batch norm folded in.
  *   fv_mfe_input_fwd, fv_motion_warp_fwd, fv_frames_u8   the inference data flow of evaluate.py: the
  *                            MFE's hourglass input, mask blend + warp, and the uint8 frame output.
+ *   fv_frames_from_u8, fv_pose_kp_fwd, fv_pose_kp_new_fwd   the uint8 way in (img_as_float32) and
+ *                            transform_kp / transform_kp_with_new_pose (utils.py:53-76) with Rs inv(Rd).
  *   fv_adam_step             torch.optim.Adam(lr, betas=(0.5,0.999)) (logger.py:60-61).
  *   fv_comm_*                distributed.py:24-31 init_process_group("nccl") + DDP's
  *                            gradient all-reduce (logger.py:55,58) + SyncBN collectives.
@@ -920,6 +922,24 @@ int fv_motion_warp_fwd(int dtype, const void* logits, const void* fs, const floa
  * out [N][H][2W][3] uint8, driving left; byte = trunc(255.0f * min(max(x, 0), 1)), one fp32 multiply
  * and a truncation, bit-equal to numpy's clip(0, 1) and (255 * a).astype(uint8).  out 4-byte aligned. */
 int fv_frames_u8(const float* driving, const float* generated, int N, int H, int W, void* out, void* stream);
+/* The way in: frames [T][H][W][3] uint8 -> out [T][3][H][W] fp32 = x * fp32(1 / 255), one rounded fp32
+ * multiply (skimage's img_as_float32, data.u8_to_float).  32-bit loads when `frames` is 4-byte aligned. */
+int fv_frames_from_u8(const void* frames, int T, int H, int W, float* out, void* stream);
+/* transform_kp (utils.py:53-59) and the motion Jacobian in one launch, all fp32:
+ * R [N][3][3] = Ry(pitch) Rx(yaw) Rz(roll) (the reference's naming of the axes), kp [N][K][3] =
+ * R (scale kp_c) + t with kp_c [Nc][K][3], Nc 1 or N, scale [N], and, for a non-null Rs [Ns][3][3] (Ns 1
+ * or N), J [N][3][3] = Rs inv(R), the inverse taken in closed form (adjugate over determinant).  Rs NULL:
+ * J is not written (and may be NULL). */
+int fv_pose_kp_fwd(const float* kp_c, const float* yaw, const float* pitch, const float* roll, const float* t,
+                   const float* scale, const float* Rs, int N, int Nc, int Ns, int K, float* kp, float* R, float* J,
+                   void* stream);
+/* transform_kp_with_new_pose (utils.py:62-76): R = Ry(new_pitch) Rx(new_yaw) Rz(new_roll), kp [N][K][3] =
+ * R kp_in + t + (R inv(R_old)) delta, R_old from (yaw, pitch, roll), then z += 0.33 - mean(z) over all
+ * N K keypoints of the call (one block, one fixed-order sum).  kp_in and delta [N][K][3].  J as above.
+ * N K <= 65536. */
+int fv_pose_kp_new_fwd(const float* kp_in, const float* yaw, const float* pitch, const float* roll, const float* t,
+                       const float* delta, const float* new_yaw, const float* new_pitch, const float* new_roll,
+                       const float* Rs, int N, int Ns, int K, float* kp, float* R, float* J, void* stream);
 
 #ifdef __cplusplus
 }

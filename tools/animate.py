@@ -9,6 +9,10 @@ reference's evaluate.py, with its flags, on facevae_amd.Animator.
 --driving    a folder of frames (sorted by name) or a .gif; the first --num_frames are used
 --output     a .gif (written through PIL), or a .npy of the [T, H, 2W, 3] uint8 frames
 
+--graph      capture the per-frame call once (Animator.capture, uint8 in and out) and stream the clip through
+             its replays, --batch frames per replay, uploads and downloads overlapping them; the last,
+             shorter chunk runs eagerly.  Not with --source f, which changes the source every frame.
+
 Each output frame is the driving frame on the left and the generated one on the right.  The
 checkpoint is <ckp_dir>/<ckp zero-filled to 8>-checkpoint.pth.tar as Logger.save_cpk writes it; its
 afe / ckd / hpe_ede / mfe / generator entries are loaded strictly (--efe: the efe entry too, whose
@@ -56,9 +60,12 @@ def main():
     ap.add_argument("--batch", type=int, default=8, help="driving frames per call")
     ap.add_argument("--dtype", choices=["bf16", "fp32"], default="bf16")
     ap.add_argument("--efe", action="store_true", help="load and apply the checkpoint's efe entry")
+    ap.add_argument("--graph", action="store_true", help="replay a captured HIP graph per chunk of --batch frames")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("animate needs a GPU")
+    if a.graph and a.source == "f":
+        raise SystemExit("--graph drives one source with every frame; --source f takes a new source per frame")
     models = checkpoint.load_reference_models(checkpoint.reference_checkpoint_path(a.ckp_dir, a.ckp), efe=a.efe)
     mode = torch.bfloat16 if a.dtype == "bf16" else torch.float32
     for m in models.values():
@@ -78,8 +85,12 @@ def main():
             source = to_nchw(data._read_frame_u8(a.source)[None])
             source = torch.nn.functional.interpolate(source, size=(256, 256))
         anim.set_source(source)
-        for i in range(0, len(video), a.batch):
-            out.append(anim.drive(to_nchw(video[i:i + a.batch]), as_uint8=True).cpu().numpy())
+        whole = len(video) // a.batch * a.batch if a.graph else 0
+        if whole:
+            cap = anim.capture(a.batch, as_uint8=True, u8_in=True)
+            out.extend(cap.stream(np.array(video[i:i + a.batch]) for i in range(0, whole, a.batch)))
+        for i in range(whole, len(video), a.batch):
+            out.append(anim.drive(to_nchw(video[i:i + a.batch]), as_uint8=True, fused_pose=a.graph).cpu().numpy())
     if not out:
         raise SystemExit(f"{a.driving}: no driving frames")
     write_frames(a.output, np.concatenate(out))

@@ -3,7 +3,9 @@ full-size networks, bf16): the Animator (facevae_amd/animate.py: cached source, 
 kernels) against the unfused composition the existing forwards give -- MFE.forward +
 Generator.forward in eval mode with the source side recomputed for every frame, as evaluate.py's
 per-frame loop does -- and, to separate the two gains, the unfused motion path on a cached source
-(fs computed once and repeated per frame).
+(fs computed once and repeated per frame).  Two more variants time the one-frame-at-a-time remedy:
+"animator_fused_pose" is drive(fused_pose=True), still eager, and "animator_graph" is the replay of
+Animator.capture(T), the copy_ of the frames into the static input included.
 
     python tools/animbench.py [--frames 1 8] [--window 0.5] [--rounds 3] [--profile-kernels]
                               [--out profiles/animate/animbench.json]
@@ -14,8 +16,10 @@ seconds per variant, the variants alternating inside this one process), the medi
 (max - min over the median) of the windows; the library entries called per drive (every fv_* entry
 is one launch or a fixed few) and, with --profile-kernels, the device kernels per call counted by
 torch's profiler (torch's own copy / cat / cast kernels included; a run of its own, not timed);
-the bytes of the intermediates the fused kernels no longer write, from the shapes; and
-"motion_breakdown": us per call of the fused launches alone against the ops they replace.
+the bytes of the intermediates the fused kernels no longer write, from the shapes;
+"motion_breakdown": us per call of the fused launches alone against the ops they replace; and
+"graph_gain": the eager Animator's median minus the replay's over the eager median, next to the larger
+of the two spreads, which it has to exceed to count as a gain.
 """
 import argparse
 import collections
@@ -169,8 +173,10 @@ def main():
                rounds=a.rounds, frames={})
     for T in a.frames:
         d = torch.rand(T, 3, a.size, a.size, generator=g, device="cuda")
+        cap = anim.capture(T)
         variants = dict(animator=lambda: anim.drive(d), unfused=lambda: unfused(d, False),
-                        unfused_cached_source=lambda: unfused(d, True))
+                        unfused_cached_source=lambda: unfused(d, True),
+                        animator_fused_pose=lambda: anim.drive(d, fused_pose=True), animator_graph=lambda: cap(d))
         out = {}
         for name, fn in variants.items():            # warm-up and the counts of one call
             fn()
@@ -191,6 +197,10 @@ def main():
         out["animator_over_unfused"] = round(out["animator"]["ms_per_frame"] / out["unfused"]["ms_per_frame"], 4)
         out["animator_over_unfused_cached_source"] = round(
             out["animator"]["ms_per_frame"] / out["unfused_cached_source"]["ms_per_frame"], 4)
+        eager, graph = out["animator"], out["animator_graph"]
+        gain = (eager["ms_per_frame"] - graph["ms_per_frame"]) / eager["ms_per_frame"]
+        out["graph_gain"] = dict(gain=round(gain, 4), larger_spread=max(eager["spread"], graph["spread"]),
+                                 above_spread=gain > max(eager["spread"], graph["spread"]))
         out["bytes_not_written"] = bytes_not_written(T, S=a.size // 4)
         out["motion_breakdown"] = motion_breakdown(T, a.window, S=a.size // 4)
         res["frames"][str(T)] = out
