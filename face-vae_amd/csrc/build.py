@@ -19,8 +19,9 @@ PKG = os.path.dirname(HERE)
 ROOT = os.path.dirname(PKG)
 OUT = os.path.join(PKG, "libfacevae.so")
 BUILD = os.path.join(HERE, "build")
-# the 2-D convolution is several files sharing conv_common.h / conv_plan.h; the longest compiles first
-SOURCES = ["conv_fwd_v2.hip", "conv_wgrad.hip", "conv_fwd.hip", "conv_halo3.hip", "conv3d_gemm.hip", "conv.hip", "abi.cpp",
+# the 2-D convolution is several files sharing conv_common.h / conv_plan.h; the longest compiles first.
+# This is the link order too: conv.hip keeps its place, conv_fp8.hip and conv_prep.hip behind it
+SOURCES = ["conv_fwd_v2.hip", "conv_wgrad.hip", "conv_fwd.hip", "conv_halo3.hip", "conv3d_gemm.hip", "conv.hip", "conv_fp8.hip", "conv_prep.hip", "abi.cpp",
            "conv3d.hip", "warp.hip", "conv_shapes.hip", "vgg.hip", "convt.hip", "bn.hip", "disc.hip", "pose.hip", "ckd.hip", "efe.hip", "tps.hip", "hopenet.hip", "animate.hip", "misc.hip", "comm.cpp"]
 HEADERS = ["common.h", "conv_common.h", "conv_plan.h", os.path.join(ROOT, "include", "facevae.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

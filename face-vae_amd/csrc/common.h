@@ -135,7 +135,7 @@ static inline FastDiv make_fastdiv(uint32_t d) {
 __device__ __forceinline__ uint32_t fdiv(uint32_t n, FastDiv f) { return (__umulhi(n, f.m) + n) >> f.s; }
 
 // ------------------------------------------------------------------------------------
-// fp8 (e4m3) delayed-scaling sites, shared by the quantize passes (conv.hip) and the BN passes
+// fp8 (e4m3) delayed-scaling sites, shared by the quantize passes (conv_fp8.hip) and the BN passes
 // that write an fp8 copy of their output (bn.hip).  site = uint32[FP8_SITE]: [0, 16) amax
 // history (float bits), [16] amax of the call in flight (float bits, atomicMax: max is
 // order-free, so deterministic), [17] history write index, [18] dq of the call in flight.

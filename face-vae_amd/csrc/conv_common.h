@@ -1,8 +1,9 @@
 // Internal header of the 2-D convolution's translation units (conv.hip, conv_fwd.hip,
-// conv_fwd_v2.hip, conv_halo3.hip, conv_shapes.hip, conv_wgrad.hip): the forward kernels' argument
-// struct, the device helpers the kernel families share, and the declarations of the generic
-// forward families' host launchers (the halo 3x3, special-shape and weight-gradient launchers, the
-// weight gradient's argument structs and the plan types: conv_plan.h).
+// conv_fwd_v2.hip, conv_halo3.hip, conv_shapes.hip, conv_wgrad.hip, conv_prep.hip, conv_fp8.hip):
+// the forward kernels' argument struct, the device helpers the kernel families share, and the
+// declarations of the generic forward families' host launchers (the halo 3x3, special-shape,
+// weight-gradient and weight-preparation launchers, their argument structs and the plan types:
+// conv_plan.h).
 // Kernels have internal linkage, so a kernel is launched only from its own file, through a
 // launcher.  Everything declared here that has linkage is hidden: the library exports the fv_*
 // entries only.
@@ -632,7 +633,7 @@ __device__ __forceinline__ void wait_vm_dyn(int n) {
 constexpr int BK2 = 64;
 __device__ __forceinline__ int swz8(int row) { return (row >> 1) & 7; }
 // 16-B chunk swizzle of the 64-B halo pixels of conv3_halo_fwd2 (conv_halo3.hip) and the fp8 halo
-// kernels (conv.hip): a fragment read of 16 consecutive halo pixels from any start is conflict free
+// kernels (conv_fp8.hip): a fragment read of 16 consecutive halo pixels from any start is conflict free
 __device__ __forceinline__ int h3swz(int hp) { return ((hp >> 2) & 1) << 1; }
 
 typedef __attribute__((address_space(3))) void* lds_ptr_t;

@@ -1,8 +1,10 @@
 // Internal header of the 2-D convolution's translation units, for what only they share (not
 // pose.hip or conv3d_gemm.hip, which include conv_common.h): the weight-gradient family's
-// argument structs, the plan types that conv.hip's planners fill, the tile constants of the
-// special-shape kernels that the planners read, and every launcher of conv_halo3.hip,
-// conv_shapes.hip and conv_wgrad.hip.  Everything declared here that has linkage is hidden.
+// argument structs, the job structs of the weight re-layout kernels, the plan types that
+// conv.hip's planners fill, the tile constants of the special-shape kernels that the planners
+// read, every launcher of conv_halo3.hip, conv_shapes.hip, conv_wgrad.hip and conv_prep.hip, and
+// the four functions of conv.hip that conv_fp8.hip calls.  Everything declared here that has
+// linkage is hidden.
 #pragma once
 #include "conv_common.h"
 
@@ -30,6 +32,49 @@ void launch_c64(const ConvArgs& a, int nblk, unsigned xb, int nbands, hipStream_
 void launch_upband(const ConvArgs& a, int nblk, unsigned xb, int nbands, hipStream_t s);     // conv3up_band_fwd
 int launch_c1s(const ConvArgs& a, int k, int bpx, int grid, unsigned xb, hipStream_t s);     // conv1x1_stream<k, bpx>
 void launch_c7n(const ConvArgs& a, int nblk, unsigned xb, int band, hipStream_t s);          // conv7_n3_fwd2
+
+// ---- job structs of the weight re-layout kernels (conv_prep.hip), filled by conv.hip's entries ----
+// weight_prep2_kernel: both layouts in one launch, blocks [0, j0.nb) write wk, the rest wt
+struct WPrepJob { void* out; int rows, Kpad, lgCin, K, transposed, nb, smaj; };
+// weight_prep_multi_kernel: one launch for the generic weight layouts of many convs
+// (fv_conv_weight_prep_multi): job j owns blocks [blk0, blk0 + nb); at most 2 * FV_WPREP_MAX
+// jobs, passed by value
+struct WPrepMJob {
+  const float* w;
+  const float* sigma;
+  void* out;
+  int rows, Kpad, lgCin, K, transposed, nb, cout, cin_valid, KS, blk0, smaj;
+};
+struct WPrepMulti {
+  int n;
+  WPrepMJob j[2 * FV_WPREP_MAX];
+};
+
+// ---- launchers of conv_prep.hip, one per kernel family: the caller decides the grid (nblk blocks
+// of the kernel's block size) and every argument; a launcher that has a dtype (FV_BF16 / FV_F32)
+// or a (mode, convt) to choose from returns non-zero for one that is not instantiated ----
+void launch_wprep_c7n(const float* wp, const float* sigma, bf16* wn, int cout, int nblk, hipStream_t s);
+int launch_wprep(int dtype, const float* wp, const float* sigma, void* wk, int rows, int Kpad, int cout, int cin_valid,
+                 int lgCin, int KS, int K, int transposed, int smaj, int nblk, hipStream_t s);   // weight_prep_kernel
+int launch_wprep_s2t(int dtype, const float* wp, const float* sigma, void* wt, int rows, int Kph, int cout,
+                     int cin_valid, int lgC, int nblk, hipStream_t s);
+int launch_wprep2(int dtype, const float* wp, const float* sigma, int cout, int cin_valid, int KS, const WPrepJob& j0,
+                  const WPrepJob& j1, int nblk, hipStream_t s);
+int launch_wprep_multi(int dtype, const WPrepMulti& m, int nbx, hipStream_t s);                  // grid (nbx, m.n)
+void launch_wprep_subpix(const float* wp, const float* sigma, bf16* wk, int rows, int Kpad, int cout, int cin_valid,
+                         int lgCin, int nblk, hipStream_t s);
+void launch_wprep_s2(const float* wp, const float* sigma, bf16* wt, int rows, int Kpad, int cout, int cin_valid,
+                     int lgCt, int nblk, hipStream_t s);
+// weight_prep_phase_kernel<mode, convt>: mode 1 / 2; cinv and gain are read with convt only
+int launch_wprep_phase(int mode, bool convt, const float* wp, const float* sigma, bf16* out, int rows, int units,
+                       int cout, int cin_valid, int cpp, const float* cinv, float gain, int nblk, hipStream_t s);
+void launch_convt_norm(const float* w, int cin, int cout, float* inv, int nblk, hipStream_t s);
+void launch_convt_wprep(const float* w, const float* inv, float gain, bf16* wk, int rows, int Kpad, int lgCin, bf16* wt,
+                        int rows_t, int lgCt, int cin_valid, int cout, int nblk, hipStream_t s);
+void launch_convt_wgrad_reduce(const float* slab, const float* bslab, float* dw, float* db, int nsplit, int CW, int KW,
+                               int cout, int cin_valid, int lgCin, int nb_main, int nb_bias, hipStream_t s);
+void launch_convt_weight_bwd(const float* w, const float* inv, float gain, float* g, int cin, int cout, int nblk,
+                             hipStream_t s);
 
 // ---- argument structs of the weight-gradient kernels (conv_wgrad.hip) ----
 struct WgArgs {
@@ -144,5 +189,11 @@ void launch_wgrad_reduce_subpix(const float* slab, const float* bslab, float* dw
                                 int cout, int cin_valid, int lgCin, int nb_main, int nb_bias, hipStream_t s);
 void launch_wgrad_reduce(const float* slab, const float* bslab, float* dw, float* db, int nsplit, int CW, int KW, int K,
                          int cout, int cin_valid, int lgCin, int KS, int nb_main, int nb_bias, int KSL, hipStream_t s);
+
+// ---- what conv_fp8.hip calls of conv.hip's checks, switches and planners (defined there, once) ----
+int check_desc(const fv_conv_desc* d);                 // FV_OK or the error of a bad descriptor
+int res_sched(int dflt);                               // FV_RES_SCHED, read per call; dflt when unset
+int sr_geometry(const fv_conv_desc* d, int* bp);       // store-pass records (and pixels per record) of d's launch
+WgPlan plan_wgrad(const fv_conv_desc* d);
 
 #pragma GCC visibility pop

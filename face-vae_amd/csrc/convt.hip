@@ -1,7 +1,8 @@
 // Generic ConvTranspose2dELR (models_utils.py:404-516) for gfx950: any kernel size / stride /
 // padding, fp32 (parity mode) or bf16 operands, NHWC activations.  Direct kernels (VALU, fp32
 // accumulation): the FaceVAE-relevant geometry k4 s2 p1 at power-of-two sizes runs on the
-// sub-pixel MFMA kernels of conv.hip instead (fv_convt_supported).
+// sub-pixel MFMA kernels of the 2-D convolution instead (fv_convt_supported in conv.hip; their
+// weight kernels: conv_prep.hip).
 //   convt_eff_weight   W_eff = gain * [1 / max(||W[:, o]||, 1e-12)] * W   (F.normalize over dims
 //                      [0, 2, 3] when demod, models_utils.py:461-470; gain 429-433)
 //   convt_direct_fwd   out[n][oh][ow][o] = b + sum_{i, r, s} x[n][ih][iw][i] W_eff[i][o][r][s],
@@ -39,7 +40,7 @@ __global__ void __launch_bounds__(256) convt_eff_weight_kernel(const float* __re
   we[e] = w[e] * (inv ? gain * inv[co] : gain);
 }
 
-// in place, one wave per output channel: G = dL/dW_eff -> dL/dW (see conv.hip convt_weight_bwd)
+// in place, one wave per output channel: G = dL/dW_eff -> dL/dW (see conv_prep.hip convt_weight_bwd_kernel)
 __global__ void __launch_bounds__(64) convt_weight_grad_kernel(const float* __restrict__ w, const float* inv,
                                                                float gain, float* g, int cin, int cout, int kk) {
   const int co = blockIdx.x, l = threadIdx.x;
