@@ -391,7 +391,7 @@ def assert_exact(got, want, what):
     rep = mismatch_report(got, want)
     if rep is None:
         return
-    names = "nchw" if got.dim() == 4 else "".join(f"d{i}" for i in range(got.dim()))
+    names = {4: "nchw", 5: "ncdhw"}.get(got.dim()) or [f"d{i}" for i in range(got.dim())]
     lines = [f"{what}: {rep['count']} of {rep['total']} elements differ from the float64 reference "
              f"(as {got.dtype}); coordinates are ({', '.join(names)})",
              "  bounding box: " + ", ".join(f"{a}..{b}" for a, b in zip(rep["lo"], rep["hi"]))
@@ -406,7 +406,7 @@ class Guarded:
     the launch.  A kernel must write every element it owns (no NaN left where the test looks) and
     nothing else (check_canary)."""
 
-    def __init__(self, shape, dtype, device="cuda", nhwc=False):
+    def __init__(self, shape, dtype, device="cuda", nhwc=False, ndhwc=False):
         numel = math.prod(shape)
         self.buf = torch.full((numel + 2 * GUARD,), CANARY, dtype=dtype, device=device)
         self.flat = self.buf[GUARD:GUARD + numel]
@@ -414,6 +414,9 @@ class Guarded:
         if nhwc:          # logical NCHW shape over NHWC memory (torch.channels_last)
             N, C, H, W = shape
             self.t = self.flat.view(N, H, W, C).permute(0, 3, 1, 2)
+        elif ndhwc:       # logical NCDHW shape over NDHWC memory (torch.channels_last_3d)
+            N, C, D, H, W = shape
+            self.t = self.flat.view(N, D, H, W, C).permute(0, 4, 1, 2, 3)
         else:
             self.t = self.flat.view(shape)
 

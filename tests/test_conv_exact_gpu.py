@@ -26,7 +26,7 @@ families) and in fp32 (the exact fp32 MFMA path):
 Not covered here, because their arithmetic is not exact on any operands: epi_sigmoid, the
 demodulated ConvTranspose path, and the mode-2 records of fv_conv2d_bwd_data_sr (transcendental
 or invstd arithmetic).  fp8 has its own elementwise gates in test_fp8_gpu.py.  The 3-D convs
-are a follow-up."""
+are held to the same equality in tests/test_conv3d_exact_gpu.py."""
 import ctypes
 
 import pytest
