@@ -77,6 +77,7 @@ _SIGS = {
     "fv_conv2d_fwd": (c_int, [D, P, P, P, P, P, P, P, P, P]),
     "fv_conv2d_bwd_data": (c_int, [D, P, c_int, P, P, P]),
     "fv_conv2d_dgrad_lowres": (c_int, [D]),
+    "fv_conv2d_fwd_kernel": (c_int, [D, c_int, c_int, c_int, c_int]),
     "fv_conv2d_wgrad_nsplit": (c_int, [D]),
     "fv_conv2d_wgrad_slab_elems": (c_size_t, [D]),
     "fv_conv2d_wgrad_bias_slab_elems": (c_size_t, [D]),
@@ -281,6 +282,19 @@ _SIGS = {
     "fv_pose_kp_fwd": (c_int, [P] * 7 + [c_int] * 4 + [P, P, P, P]),
     "fv_pose_kp_new_fwd": (c_int, [P] * 10 + [c_int] * 3 + [P, P, P, P]),
 }
+
+# fv_conv2d_fwd_kernel's result (FV_CONVK_* of facevae.h, in order) -> name
+CONV_KERNELS = ("V1", "V2", "C1S", "HALO3_FWD3", "HALO3_FWD2", "SUBPIX_V2", "SUBPIX_HALO", "UPBAND", "HALO7", "C74",
+                "C64", "C7N", "DGRAD_LOWRES_HALO", "DGRAD_LOWRES_V2")
+
+
+def conv_kernel(d, dgrad=False, res=False, stats=False, sr_mode=0):
+    """Name of the kernel family fv_conv2d_fwd (fv_conv2d_bwd_data with dgrad) dispatches descriptor d to."""
+    k = query("fv_conv2d_fwd_kernel", ctypes.byref(d), int(dgrad), int(res), int(stats), int(sr_mode))
+    if k < 0:
+        raise FaceVAELibError("fv_conv2d_fwd_kernel: " + load().fv_last_error().decode(errors="replace"))
+    return CONV_KERNELS[k]
+
 
 _lib = None
 

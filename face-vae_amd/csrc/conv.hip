@@ -103,13 +103,12 @@ int wrows(int rows_needed) {
 // upsample + 3x3 conv as 4 sub-pixel phases of a 2x2 conv over the low-res input (bf16 v2
 // path; FV_DISABLE_SUBPIX=1 keeps the folded-upsample 3x3 kernel).  2.25x fewer MACs than the
 // reference formulation (reported utilisation still uses the reference FLOPs).
-static int g_disable_subpix = -1;
+bool subpix_disabled() {     // FV_DISABLE_SUBPIX, read once
+  static const bool off = [] { const char* e = getenv("FV_DISABLE_SUBPIX"); return e && e[0] == '1'; }();
+  return off;
+}
 bool use_subpix(const fv_conv_desc* d) {
-  if (g_disable_subpix < 0) {
-    const char* e = getenv("FV_DISABLE_SUBPIX");
-    g_disable_subpix = (e && e[0] == '1') ? 1 : 0;
-  }
-  if (g_disable_subpix || !d->upsample || d->ksize != 3 || !use_v2(d)) return false;
+  if (subpix_disabled() || !d->upsample || d->ksize != 3 || !use_v2(d)) return false;
   const int hl = d->h / 2, wl = d->w / 2;
   if (fv_ilog2(hl) < 0 || fv_ilog2(wl) < 0 || wl % 16) return false;
   const long pl = (long)d->n * hl * wl;
@@ -137,17 +136,15 @@ namespace {
 // stride-2 4x4 conv over dy (bf16 v2 path; replaces dgrad at the high resolution followed by
 // the 2x2 sum of fv_upsample2x_bwd: 0.44x the MACs, one pass fewer)
 bool use_dgrad_lowres(const fv_conv_desc* d) {
-  if (g_disable_subpix < 0) use_subpix(d);     // reads FV_DISABLE_SUBPIX
-  if (g_disable_subpix || !d->upsample || d->ksize != 3 || d->dtype != FV_BF16) return false;
+  if (subpix_disabled() || !d->upsample || d->ksize != 3 || d->dtype != FV_BF16) return false;
   const int ct = pad_pow2_8(d->cout);
   if (ct % 64 || d->cin % 8 || (d->w / 2) % 16) return false;
   return (long)d->n * d->h * d->w * ct * 2 < (1L << 31);
 }
 
 // UpBlock2D forward with a 128-channel input on the sliding-band kernel (conv3up_band_fwd).
-// Its weights are the plain sub-pixel layout.
+// Its weights are the plain sub-pixel layout.  (This and use_subpix_halo: given use_subpix(d).)
 static bool use_upband(const fv_conv_desc* d) {
-  if (d->dtype != FV_BF16 || !use_subpix(d)) return false;
   const int hl = d->h / 2, wl = d->w / 2;
   return d->cin == 128 && d->cin_valid == 128 && d->cout % 64 == 0 && wl % 32 == 0 && hl % 8 == 0 &&
          !d->out_nchw_f32 && !d->epi_sigmoid && !d->pro_act && d->ldy % 8 == 0 &&
@@ -156,15 +153,14 @@ static bool use_upband(const fv_conv_desc* d) {
 // the other UpBlock2D convs on the halo kernel (conv3_halo_fwd3 MODE 1 forward; MODE 2 low-res
 // data gradient: dgrad_halo_bn); shapes outside these conditions run conv_fwd_v2 MODE 2 / 3
 static bool use_subpix_halo(const fv_conv_desc* d) {
-  if (!use_subpix(d) || use_upband(d)) return false;
   const int hl = d->h / 2, wl = d->w / 2;
   return d->cout % 64 == 0 && d->cin % 32 == 0 && d->cin >= 64 && d->cin_valid == d->cin && wl % 64 == 0 &&
          hl % 4 == 0 && !d->out_nchw_f32 && !d->epi_sigmoid && !d->pro_act && d->ldy % 8 == 0 &&
          (long)d->n * hl * wl * d->cin * 2 < (1L << 31) && (long)d->n * d->h * d->w * d->ldy * 2 < (1L << 31);
 }
 // co tile (256 / 128 rows) of the low-res data gradient on the halo kernel, 0 = not on it
+// (given use_dgrad_lowres(d))
 static int dgrad_halo_bn(const fv_conv_desc* d) {
-  if (!use_dgrad_lowres(d)) return 0;
   const int hl = d->h / 2, wl = d->w / 2;
   if (pad_pow2_8(d->cout) != d->cout || d->cout % 32 || wl % 64 || hl % 4 || d->cin_valid != d->cin) return 0;
   if ((long)d->n * d->h * d->w * d->cout * 2 >= (1L << 31)) return 0;
@@ -277,6 +273,27 @@ static bool use_upw(const fv_conv_desc* d) {
   return d->dtype == FV_BF16 && d->upsample && d->ksize == 3 && !d->pro_act && d->cin % 64 == 0 &&
          d->cin_valid == d->cin && d->cout % 64 == 0 && d->w % 64 == 0 && d->h % 4 == 0;
 }
+// the register-staged kernel's tile, and the tiles, splits and slab of a plan whose tile is set
+// (the tail of plan_wgrad and all of plan_wgrad_s2)
+void wg_v1_tile(WgPlan* p, int cout) {
+  p->bc = cout > 64 ? 128 : (cout > 16 ? 64 : 16);
+  p->bkt = 128;
+  p->px = 32;
+}
+void wg_split(WgPlan* p, int K, int cout, long P) {
+  p->ntk = fv_cdiv(K, p->bkt);
+  p->ntc = fv_cdiv(cout, p->bc);
+  p->nsteps = fv_cdiv(P, p->px);
+  const int ntile = p->ntk * p->ntc;
+  // v2: about 256 blocks (128: 1x1 weight gradients 45 / 33 -> 67 / 40 us)
+  int ns = p->v2 ? (256 + ntile / 2) / ntile : 768 / ntile;
+  if (ns < 1) ns = 1;
+  if (ns > p->nsteps) ns = p->nsteps;
+  p->sps = fv_cdiv(p->nsteps, ns);
+  p->nsplit = fv_cdiv(p->nsteps, p->sps);
+  p->KW = p->ntk * p->bkt;
+  p->CW = p->ntc * p->bc;
+}
 
 }  // namespace
 
@@ -290,8 +307,8 @@ WgPlan plan_wgrad(const fv_conv_desc* d) {
   // every caller passes; fv_conv2d_bwd_weight re-checks the real stride) must stay < 2 GB
   const bool fits = d->dtype == FV_BF16 && (long)d->n * hin * win * d->cin * 2 < (1L << 31) &&
                    P * pad_pow2_8(d->cout) * 2 < (1L << 31);
-  p.v2 = fits && !d->pro_act;
-  // out_conv 7x7 64 -> <= 4 (v2 == 3): blocks = (image, 64-column strip, row segment), about
+  p.v2 = fits && !d->pro_act ? WG_V2 : WG_V1;
+  // out_conv 7x7 64 -> <= 4 (WG_C7): blocks = (image, 64-column strip, row segment), about
   // 2 per CU (r6: 1024 -> 512 blocks halves the 58.7 MB of slabs; out_conv weight gradient
   // 98.4 -> 90.4 us + reduce 15 -> 10.6 us, step -0.03 ms; 256 blocks: 114 us;
   // profiles/r6/r6k_ab_wgrad_blocks.log); slab [block][32 (r, co)][448 (s, ci)]
@@ -300,7 +317,7 @@ WgPlan plan_wgrad(const fv_conv_desc* d) {
     int nseg = fv_cdiv(512, d->n * strips);
     if (nseg > fv_cdiv(d->h, 8)) nseg = fv_cdiv(d->h, 8);
     if (nseg < 1) nseg = 1;
-    p.v2 = 3;
+    p.v2 = WG_C7;
     p.sps = fv_cdiv(d->h, nseg);                 // rows per segment
     p.nsteps = fv_cdiv(d->h, p.sps);             // segments
     p.nsplit = d->n * strips * p.nsteps;
@@ -309,11 +326,11 @@ WgPlan plan_wgrad(const fv_conv_desc* d) {
     p.ntk = p.ntc = 1;
     return p;
   }
-  // 3x3 sliding-row wgrad (v2 == 5, conv3_halo_wgrad2): blocks = (image, 64-column strip,
+  // 3x3 sliding-row wgrad (WG_H3S, conv3_halo_wgrad2): blocks = (image, 64-column strip,
   // row segment) x co tiles of 128, ~1 block per CU; splits = image x strip x segment
   if (fits && use_h3w(d)) {
     const int strips = d->w / 64;
-    p.v2 = 5;
+    p.v2 = WG_H3S;
     p.ntc = d->cout / 128;
     p.ntk = d->cin / 64;               // 64-channel input tiles
     int nseg = (256 / (p.ntc * p.ntk) + d->n * strips / 2) / (d->n * strips);
@@ -326,11 +343,11 @@ WgPlan plan_wgrad(const fv_conv_desc* d) {
     p.KW = K;
     return p;
   }
-  // 7x7 halo path (v2 == 2): one persistent block per CU, ntk = 1 (all k in one tile)
+  // 7x7 halo path (WG_HALO7): one persistent block per CU, ntk = 1 (all k in one tile)
   const int htr = halo_wg_tr(d);
   if (p.v2 && htr) {
     const int nt = d->cin == 8 ? 4 : 1;
-    p.v2 = 2;
+    p.v2 = WG_HALO7;
     p.bkt = halo_wg_pk(d) ? 7 * 32 : fv_cdiv(K, 16) * 16;
     p.bc = nt * 16;
     p.px = htr * 64;
@@ -344,11 +361,11 @@ WgPlan plan_wgrad(const fv_conv_desc* d) {
     return p;
   }
   if (fits && use_upw(d)) {
-    // sub-pixel sliding-row weight gradient (v2 == 6, conv3_up_wgrad): blocks = (co tile, ci
+    // sub-pixel sliding-row weight gradient (WG_UP, conv3_up_wgrad): blocks = (co tile, ci
     // tile) x splits of `sps` consecutive (image, 64-column output strip) units, ~one block per
     // CU; slab [phase][split][co][4 cin] as the v2 sub-pixel path
     p.sub = 1;
-    p.v2 = 6;
+    p.v2 = WG_UP;
     p.ntc = d->cout / 64;
     p.ntk = d->cin / 64;
     const int units = d->n * (d->w / 64), tiles = p.ntc * p.ntk;
@@ -393,46 +410,19 @@ WgPlan plan_wgrad(const fv_conv_desc* d) {
     p.bc = c.bc;
     p.px = c.px;
   } else {
-    p.bc = d->cout > 64 ? 128 : (d->cout > 16 ? 64 : 16);
-    p.bkt = 128;
-    p.px = 32;
+    wg_v1_tile(&p, d->cout);
   }
-  p.ntk = fv_cdiv(K, p.bkt);
-  p.ntc = fv_cdiv(d->cout, p.bc);
-  p.nsteps = fv_cdiv(P, p.px);
-  const int ntile = p.ntk * p.ntc;
-  // v2: about 256 blocks (128: 1x1 weight gradients 45 / 33 -> 67 / 40 us)
-  int ns = p.v2 ? (256 + ntile / 2) / ntile : 768 / ntile;
-  if (ns < 1) ns = 1;
-  if (ns > p.nsteps) ns = p.nsteps;
-  p.sps = fv_cdiv(p.nsteps, ns);
-  p.nsplit = fv_cdiv(p.nsteps, p.sps);
-  p.KW = p.ntk * p.bkt;
-  p.CW = p.ntc * p.bc;
+  wg_split(&p, K, d->cout, P);
   return p;
 }
 
 namespace {
 
-// the weight gradient's plan: the generic kernel's tiles (plan_wgrad's fp32 branch) for both dtypes
+// the stride-2 weight gradient's plan: the generic kernel's tiles (plan_wgrad's fp32 branch) for both dtypes
 WgPlan plan_wgrad_s2(const fv_conv_desc* d) {
   WgPlan p{};
-  const int K = 9 * d->cin;
-  const long P = (long)d->n * d->h * d->w;
-  p.bc = d->cout > 64 ? 128 : (d->cout > 16 ? 64 : 16);
-  p.bkt = 128;
-  p.px = 32;
-  p.ntk = fv_cdiv(K, p.bkt);
-  p.ntc = fv_cdiv(d->cout, p.bc);
-  p.nsteps = fv_cdiv(P, p.px);
-  const int ntile = p.ntk * p.ntc;
-  int ns = 768 / ntile;
-  if (ns < 1) ns = 1;
-  if (ns > p.nsteps) ns = p.nsteps;
-  p.sps = fv_cdiv(p.nsteps, ns);
-  p.nsplit = fv_cdiv(p.nsteps, p.sps);
-  p.KW = p.ntk * p.bkt;
-  p.CW = p.ntc * p.bc;
+  wg_v1_tile(&p, d->cout);
+  wg_split(&p, 9 * d->cin, d->cout, (long)d->n * d->h * d->w);
   return p;
 }
 // descriptor and size checks shared by the fv_conv2d_s2_* entries
@@ -456,31 +446,6 @@ int check_s2_in(const fv_conv_desc* d, int in_h, int in_w) {
 }
 
 }  // namespace
-
-extern "C" {
-
-size_t fv_conv_wk_elems(const fv_conv_desc* d) {
-  if (check_desc(d) != FV_OK) return 0;
-  const size_t rows = (size_t)wrows(d->cout);
-  if (use_c7n(d)) return 32 * 448;
-  if (use_subpix_halo(d)) return (size_t)phase_wk_elems(d);
-  if (use_subpix(d)) return 4 * rows * kpad_of(2, d->cin);
-  return rows * kpad_of(d->ksize, d->cin);
-}
-
-size_t fv_conv_wt_elems(const fv_conv_desc* d) {
-  if (check_desc(d) != FV_OK) return 0;
-  const int cin_t = pad_pow2_8(d->cout);
-  const size_t rows = (size_t)wrows(d->cin);
-  if (dgrad_halo_bn(d)) return (size_t)phase_wt_elems(d);
-  if (use_dgrad_lowres(d)) return rows * 16 * cin_t;
-  return rows * kpad_of(d->ksize, cin_t);
-}
-
-int fv_conv2d_dgrad_lowres(const fv_conv_desc* d) {
-  if (check_desc(d) != FV_OK) return 0;
-  return use_dgrad_lowres(d) ? 1 : 0;
-}
 
 // 7x7 halo path: (cin 8 -> cout 64, TR 8, weights in LDS) or (cin 64 -> cout <= 16, TR 2)
 static int halo_tr(const fv_conv_desc* d) {
@@ -524,60 +489,177 @@ static int c64_bands(const fv_conv_desc* d) {
   while (base * nb < 256 && d->h % (nb * 64) == 0) nb *= 2;
   return nb;
 }
-static FwdTile plan_tile(const fv_conv_desc* d) {
-  const int tr = halo_tr(d);
-  if (tr) return {d->cout <= 16 ? 16 : 64, tr * 64};
-  return use_v2(d) ? fwd_tile_v2(d->cout) : fwd_tile(d->cout);
+// 1x1 convs with K = 256 / 512 input channels and whole 256-channel output groups (the mid
+// convs and their data gradients) on the pixel-stream kernel conv1x1_stream; FV_C1S=0 keeps
+// conv_fwd_v2 (A/B).  Read per call.
+static bool use_c1s(const fv_conv_desc* d) {
+  const char* e = getenv("FV_C1S");
+  if (e && e[0] == '0') return false;
+  if (!use_v2(d) || d->ksize != 1 || d->upsample || d->pro_act) return false;
+  if ((d->cin != 256 && d->cin != 512) || d->cout % 256 || d->ldy != d->cout) return false;
+  const long P = (long)d->n * d->h * d->w;
+  return P % (32768 / d->cin) == 0 && P * d->cout * 2 < (1L << 31);   // (both tile sizes)
 }
 
-// pixels per BN-statistics record = the pixels of one wave row of the tile (BM / WM)
-static int stats_record_pixels(const fv_conv_desc* d) {
-  if (use_c7n(d)) return 64;
-  if (use_upband(d)) return UPB_G * 2 * 32;                  // (block, 4 iterations, phase)
-  if (use_subpix_halo(d)) return 128;                         // (tile, wave row, phase): RM * 16                                  // one 64-pixel row segment
-  if (use_c74(d)) return c74_tiles_per_block(d) * C74_TR * 64;   // one record per block
-  if (use_c64(d)) return C64_G * 64;                          // 8 iterations x one wave's row
-  if (halo_tr(d)) return plan_tile(d).bm / 8;                 // 8 waves stacked over pixels
-  const FwdTile t = plan_tile(d);
-  if (const int bn = halo3_bn(d)) return bn == 256 ? 128 : 64;   // RM * 16 pixels per wave row
-  if (use_v2(d)) {
-    if (t.bn == 64 || t.bn == 16 || (t.bn == 128 && t.bm == 256)) return t.bm / 4;
-    return t.bm / 2;                                          // 128x128, 256x256, 256x128
+// the forward-conv descriptor the data gradient of `d` runs as (transposed, flipped weights)
+static fv_conv_desc dgrad_desc(const fv_conv_desc* d) {
+  fv_conv_desc t{};
+  t.dtype = d->dtype;
+  t.n = d->n; t.h = d->h; t.w = d->w;
+  t.cin = pad_pow2_8(d->cout);
+  t.cin_valid = d->cout;
+  t.cout = d->cin;   // every (padded) input channel; padded ones come out 0
+  t.ldy = d->cin;
+  t.ksize = d->ksize;
+  return t;
+}
+
+// The forward plan: the use_*() conditions above are asked here, in the order of the launch, and
+// nowhere else.  Everything but `kind` is a function of the descriptor alone (FV_C1S only swaps
+// V2 and C1S, which share tile, records and weight image).
+FwdPlan plan_fwd(const fv_conv_desc* d) {
+  FwdPlan p{};
+  const long P = (long)d->n * d->h * d->w;
+  auto set = [&p](FwdKind k, int bn, int tr, int bm, int rec_px) {
+    p.kind = k; p.bn = bn; p.tr = tr; p.bm = bm; p.rec_px = rec_px;
+  };
+  // BN-statistics records of the generic kernels: the pixels of one wave row of the tile (BM / WM)
+  auto set_v2 = [&](FwdKind k, int rec_px) {
+    const FwdTile t = fwd_tile_v2(d->cout);
+    const bool wm4 = t.bn == 64 || t.bn == 16 || (t.bn == 128 && t.bm == 256);   // else 128x128, 256x256, 256x128
+    set(k, t.bn, 0, t.bm, rec_px ? rec_px : wm4 ? t.bm / 4 : t.bm / 2);
+  };
+  // the generic image [rows][Kpad]: whole co tiles of every kernel that may read it (wrows)
+  p.wrows = wrows(d->cout);
+  p.wlen = kpad_of(d->ksize, d->cin);
+  p.welems = (long)p.wrows * p.wlen;
+  if (use_c7n(d)) {
+    set(FV_CONVK_C7N, 4, 0, 0, 64);                                  // one 64-pixel row segment
+    p.wrows = p.wlen = 0;
+    p.welems = 32 * 448;
+  } else if (use_c64(d)) {
+    set_v2(FV_CONVK_C64, C64_G * 64);                                // 8 iterations x one wave's row
+  } else if (const int tr = halo_tr(d)) {
+    if (use_c74(d)) {
+      set(FV_CONVK_C74, 64, C74_TR, C74_TR * 64, c74_tiles_per_block(d) * C74_TR * 64);   // one record per block
+      p.wlay = 2;
+      p.wlen = C74_K;       // the packed rows are C74_K long (the image keeps the generic size)
+    } else {
+      set(FV_CONVK_HALO7, d->cout <= 16 ? 16 : 64, tr, tr * 64, tr * 64 / 8);   // 8 waves stacked over pixels
+    }
+  } else if (use_subpix(d)) {
+    p.wlen = kpad_of(2, d->cin);                                      // 4 phase images of 2x2 taps
+    p.welems = 4L * p.wrows * p.wlen;
+    if (use_upband(d)) {
+      set(FV_CONVK_UPBAND, 64, 0, 0, UPB_G * 2 * 32);                // (block, 4 iterations, phase)
+    } else if (use_subpix_halo(d)) {
+      set(FV_CONVK_SUBPIX_HALO, 64, 4, 256, 128);                    // (tile, wave row, phase): RM * 16
+      p.wrows = p.wlen = 0;
+      p.welems = phase_wk_elems(d);
+    } else {
+      set_v2(FV_CONVK_SUBPIX_V2, 0);
+    }
+  } else if (const int bn = halo3_bn(d)) {
+    // conv3_halo_fwd3 for the 256 / 128-channel co tiles and the 8-row form of the 64-channel one,
+    // conv3_halo_fwd2 otherwise (the measurements: conv_run)
+    const bool c64k = d->cin % 64 == 0;
+    const int tr = (bn == 64 && d->h % 8 == 0 && c64k) ? 8 : 4;
+    set((bn >= 128 ? c64k : tr == 8) ? FV_CONVK_HALO3_FWD3 : FV_CONVK_HALO3_FWD2, bn, tr, tr * 64,
+        bn == 256 ? 128 : 64);                                        // RM * 16 pixels per wave row
+    p.wlay = 1;             // stage-major (weight_prep_body smaj): units of wrows rows x 32
+    // store-pass records: 256-pixel tiles of 8 waves (co tiles of 256 / 128) or 4 waves (co tiles
+    // of 64), one record per (tile, wave)
+    if (d->cout % bn == 0 && P % 256 == 0) {
+      const int nw = bn == 64 ? 4 : 8;
+      p.sr_px = 256 / nw;
+      p.sr_n = (int)(P / 256 * nw);
+    }
+  } else if (use_v2(d)) {
+    set_v2(use_c1s(d) ? FV_CONVK_C1S : FV_CONVK_V2, 0);
+  } else {
+    const FwdTile t = fwd_tile(d->cout);
+    set(FV_CONVK_V1, t.bn, 0, t.bm, t.bn == 16 ? t.bm / 4 : t.bm / 2);   // launch_fwd_ks
   }
-  return t.bn == 16 ? t.bm / 4 : t.bm / 2;                    // v1 layouts (launch_fwd_ks)
+  return p;
+}
+
+// The data gradient: directly at the low resolution for an upsample conv that qualifies, else the
+// forward of the transposed descriptor.
+FwdPlan plan_dgrad(const fv_conv_desc* d) {
+  if (!use_dgrad_lowres(d)) {
+    const fv_conv_desc t = dgrad_desc(d);
+    return plan_fwd(&t);
+  }
+  FwdPlan p{};
+  if (const int bn = dgrad_halo_bn(d)) {
+    p.kind = FV_CONVK_DGRAD_LOWRES_HALO;
+    p.bn = bn; p.tr = 4; p.bm = 256;
+    p.welems = phase_wt_elems(d);
+  } else {
+    const FwdTile t = fwd_tile_v2(d->cin);
+    p.kind = FV_CONVK_DGRAD_LOWRES_V2;
+    p.bn = t.bn; p.bm = t.bm;
+    p.wrows = wrows(d->cin);
+    p.wlen = 16 * pad_pow2_8(d->cout);                                // 4x4 taps
+    p.welems = (long)p.wrows * p.wlen;
+  }
+  return p;
+}
+
+// What one call launches.  The 64-channel band kernel has no residual / store-pass epilogue and
+// the 1x1 stream kernel no residual, statistics or store pass: such a call runs conv_fwd_v2.  It
+// may, because the plan gives both kinds conv_fwd_v2's tile and the plain [rows][Kpad] image that
+// covers whole tiles of it (wrows), and every use_c64 / use_c1s descriptor passes use_v2.
+FwdKind fwd_kind(const FwdPlan& p, bool res, bool stats, int sr_mode) {
+  if (p.kind == FV_CONVK_C64 && (res || sr_mode)) return FV_CONVK_V2;
+  if (p.kind == FV_CONVK_C1S && (res || stats || sr_mode)) return FV_CONVK_V2;
+  return p.kind;
+}
+
+// store-pass record geometry (fv_store_reduce) of the launch `d` takes: records and pixels per
+// record, 0 when that path has none (the halo-staged 3x3 kernels only have them).
+// (declared in conv_plan.h: fv_conv2d_fwd_fp8_site_sr of conv_fp8.hip checks its records with it)
+int sr_geometry(const fv_conv_desc* d, int* bp) {
+  const FwdPlan p = plan_fwd(d);
+  if (bp && p.sr_n) *bp = p.sr_px;
+  return p.sr_n;
+}
+
+// the image is one the generic re-layout kernels (weight_prep_kernel and its batched forms) write
+static bool wprep_generic(const FwdPlan& p) {
+  switch (p.kind) {
+    case FV_CONVK_C7N: case FV_CONVK_UPBAND: case FV_CONVK_SUBPIX_HALO: case FV_CONVK_SUBPIX_V2:
+    case FV_CONVK_DGRAD_LOWRES_HALO: case FV_CONVK_DGRAD_LOWRES_V2: return false;
+    default: return true;
+  }
+}
+
+extern "C" {
+
+size_t fv_conv_wk_elems(const fv_conv_desc* d) {
+  return check_desc(d) == FV_OK ? (size_t)plan_fwd(d).welems : 0;
+}
+
+size_t fv_conv_wt_elems(const fv_conv_desc* d) {
+  return check_desc(d) == FV_OK ? (size_t)plan_dgrad(d).welems : 0;
+}
+
+int fv_conv2d_dgrad_lowres(const fv_conv_desc* d) {
+  return check_desc(d) == FV_OK && plan_dgrad(d).kind >= FV_CONVK_DGRAD_LOWRES_HALO ? 1 : 0;
+}
+
+int fv_conv2d_fwd_kernel(const fv_conv_desc* d, int dgrad, int has_res, int has_stats, int sr_mode) {
+  if (check_desc(d) != FV_OK) return -1;
+  return fwd_kind(dgrad ? plan_dgrad(d) : plan_fwd(d), has_res, has_stats, sr_mode);
 }
 
 int fv_conv2d_stats_block_pixels(const fv_conv_desc* d) {
-  if (check_desc(d) != FV_OK) return 0;
-  return stats_record_pixels(d);
+  return check_desc(d) == FV_OK ? plan_fwd(d).rec_px : 0;
 }
 
 int fv_conv2d_stats_blocks(const fv_conv_desc* d) {
-  if (check_desc(d) != FV_OK) return 0;
-  return fv_cdiv((long)d->n * d->h * d->w, stats_record_pixels(d));
+  return check_desc(d) == FV_OK ? fv_cdiv((long)d->n * d->h * d->w, plan_fwd(d).rec_px) : 0;
 }
-
-static fv_conv_desc dgrad_desc(const fv_conv_desc* d);
-
-// the launch of forward-conv descriptor fd runs a halo 3x3 kernel (conv_run's halo3 branch:
-// conv3_halo_fwd3 / fwd2), whose weights are prepared stage-major (weight_prep_body smaj) with
-// wk_rows(fd) rows per tap unit
-static bool h3s_layout(const fv_conv_desc* fd) {
-  return !use_c7n(fd) && !halo_tr(fd) && !use_subpix(fd) && !use_c64(fd) && halo3_bn(fd) != 0;
-}
-static int wk_rows(const fv_conv_desc* fd) {
-  return wrows(fd->cout);
-}
-static int lay_of(const fv_conv_desc* fd) { return use_c74(fd) ? 2 : h3s_layout(fd) ? 1 : 0; }
-// ... for the forward weights (wk) and the data gradient's transposed weights (wt) of conv d
-static int smaj_wk(const fv_conv_desc* d) { return lay_of(d); }
-static int smaj_wt(const fv_conv_desc* d) {
-  if (use_dgrad_lowres(d)) return 0;
-  const fv_conv_desc t = dgrad_desc(d);
-  return lay_of(&t);
-}
-// row length of a prepared image: the packed 7x7 layout's rows are C74_K long
-static int kpad_lay(int lay, int kpad) { return lay == 2 ? C74_K : kpad; }
 
 int fv_conv_weight_prep(const fv_conv_desc* d, const float* w_param, const float* sigma, void* wk,
                         void* wt, void* stream) {
@@ -585,67 +667,54 @@ int fv_conv_weight_prep(const fv_conv_desc* d, const float* w_param, const float
   if (st) return st;
   hipStream_t s = (hipStream_t)stream;
   const int ks = d->ksize;
-  const bool generic_wk = wk && !use_c7n(d) && !use_subpix(d);
-  const bool generic_wt = wt && !use_dgrad_lowres(d);
-  if (generic_wk && generic_wt) {
+  const int cin_t = pad_pow2_8(d->cout);
+  const FwdPlan pk = plan_fwd(d), pt = plan_dgrad(d);
+  if (wk && wt && wprep_generic(pk) && wprep_generic(pt)) {
     // the common case: forward and transposed layouts in one launch
-    const int cin_t = pad_pow2_8(d->cout);
-    WPrepJob j0{wk, wrows(d->cout), kpad_lay(smaj_wk(d), kpad_of(ks, d->cin)), fv_ilog2(d->cin),
-                ks * ks * d->cin, 0, 0, smaj_wk(d)};
-    WPrepJob j1{wt, wrows(d->cin), kpad_lay(smaj_wt(d), kpad_of(ks, cin_t)), fv_ilog2(cin_t),
-                ks * ks * cin_t, 1, 0, smaj_wt(d)};
+    WPrepJob j0{wk, pk.wrows, pk.wlen, fv_ilog2(d->cin), ks * ks * d->cin, 0, 0, pk.wlay};
+    WPrepJob j1{wt, pt.wrows, pt.wlen, fv_ilog2(cin_t), ks * ks * cin_t, 1, 0, pt.wlay};
     j0.nb = (int)std::min<long>(fv_cdiv((long)j0.rows * j0.Kpad, 256), 4096);
     j1.nb = (int)std::min<long>(fv_cdiv((long)j1.rows * j1.Kpad, 256), 4096);
     FV_REQUIRE(!launch_wprep2(d->dtype, w_param, sigma, d->cout, d->cin_valid, ks, j0, j1, j0.nb + j1.nb, s),
                "weight prep: dtype %d unsupported", d->dtype);
     return fv_check_launch("weight_prep2");
   }
-  // the stage-major / packed layouts (smaj) are bf16 layouts: the fp32 images are plain
-  const bool bf = d->dtype == FV_BF16;
-  if (wk && use_c7n(d)) {
+  // (the stage-major / packed layouts are bf16 layouts: every kind that has one is a bf16 kind,
+  // so the fp32 images are plain)
+  if (wk && pk.kind == FV_CONVK_C7N) {
     launch_wprep_c7n(w_param, sigma, (bf16*)wk, d->cout, 56, s);
     if ((st = fv_check_launch("weight_prep_c7n"))) return st;
-  } else if (wk && use_subpix_halo(d)) {
-    const int nb = (int)std::min<long>(fv_cdiv(phase_wk_elems(d), 256), 4096);
+  } else if (wk && pk.kind == FV_CONVK_SUBPIX_HALO) {
+    const int nb = (int)std::min<long>(fv_cdiv(pk.welems, 256), 4096);
     FV_REQUIRE(!launch_wprep_phase(1, false, w_param, sigma, (bf16*)wk, 4 * d->cout, 4 * (d->cin / 32), d->cout,
                                    d->cin_valid, 0, nullptr, 1.f, nb, s),
                "weight prep: phase layout unsupported");
     if ((st = fv_check_launch("weight_prep_phase1"))) return st;
-  } else if (wk && use_subpix(d)) {
-    const int rows = wrows(d->cout), Kp = kpad_of(2, d->cin);
-    const long tot = 4L * rows * Kp;
-    const int nb = (int)std::min<long>(fv_cdiv(tot, 256), 4096);
-    launch_wprep_subpix(w_param, sigma, (bf16*)wk, rows, Kp, d->cout, d->cin_valid, fv_ilog2(d->cin), nb, s);
+  } else if (wk && !wprep_generic(pk)) {     // SUBPIX_V2, UPBAND: the plain sub-pixel images
+    const int nb = (int)std::min<long>(fv_cdiv(pk.welems, 256), 4096);
+    launch_wprep_subpix(w_param, sigma, (bf16*)wk, pk.wrows, pk.wlen, d->cout, d->cin_valid, fv_ilog2(d->cin), nb, s);
     if ((st = fv_check_launch("weight_prep_subpix"))) return st;
   } else if (wk) {
-    const int rows = wrows(d->cout), Kp = kpad_lay(smaj_wk(d), kpad_of(ks, d->cin));
-    const long tot = (long)rows * Kp;
-    const int nb = (int)std::min<long>(fv_cdiv(tot, 256), 4096);
-    FV_REQUIRE(!launch_wprep(d->dtype, w_param, sigma, wk, rows, Kp, d->cout, d->cin_valid, fv_ilog2(d->cin), ks,
-                             ks * ks * d->cin, 0, bf ? smaj_wk(d) : 0, nb, s),
+    const int nb = (int)std::min<long>(fv_cdiv((long)pk.wrows * pk.wlen, 256), 4096);
+    FV_REQUIRE(!launch_wprep(d->dtype, w_param, sigma, wk, pk.wrows, pk.wlen, d->cout, d->cin_valid, fv_ilog2(d->cin),
+                             ks, ks * ks * d->cin, 0, pk.wlay, nb, s),
                "weight prep: dtype %d unsupported", d->dtype);
     if ((st = fv_check_launch("weight_prep"))) return st;
   }
-  if (wt && dgrad_halo_bn(d)) {
-    const int nb = (int)std::min<long>(fv_cdiv(phase_wt_elems(d), 256), 4096);
+  if (wt && pt.kind == FV_CONVK_DGRAD_LOWRES_HALO) {
+    const int nb = (int)std::min<long>(fv_cdiv(pt.welems, 256), 4096);
     FV_REQUIRE(!launch_wprep_phase(2, false, w_param, sigma, (bf16*)wt, d->cin, 4 * (4 * d->cout / 32), d->cout,
                                    d->cin_valid, d->cout / 32, nullptr, 1.f, nb, s),
                "weight prep: phase layout unsupported");
     if ((st = fv_check_launch("weight_prep_phase2"))) return st;
-  } else if (wt && use_dgrad_lowres(d)) {
-    const int cin_t = pad_pow2_8(d->cout);
-    const int rows = wrows(d->cin), Kp = 16 * cin_t;
-    const long tot = (long)rows * Kp;
-    const int nb = (int)std::min<long>(fv_cdiv(tot, 256), 4096);
-    launch_wprep_s2(w_param, sigma, (bf16*)wt, rows, Kp, d->cout, d->cin_valid, fv_ilog2(cin_t), nb, s);
+  } else if (wt && pt.kind == FV_CONVK_DGRAD_LOWRES_V2) {
+    const int nb = (int)std::min<long>(fv_cdiv(pt.welems, 256), 4096);
+    launch_wprep_s2(w_param, sigma, (bf16*)wt, pt.wrows, pt.wlen, d->cout, d->cin_valid, fv_ilog2(cin_t), nb, s);
     if ((st = fv_check_launch("weight_prep_s2"))) return st;
   } else if (wt) {
-    const int cin_t = pad_pow2_8(d->cout);
-    const int rows = wrows(d->cin), Kp = kpad_lay(smaj_wt(d), kpad_of(ks, cin_t));
-    const long tot = (long)rows * Kp;
-    const int nb = (int)std::min<long>(fv_cdiv(tot, 256), 4096);
-    FV_REQUIRE(!launch_wprep(d->dtype, w_param, sigma, wt, rows, Kp, d->cout, d->cin_valid, fv_ilog2(cin_t), ks,
-                             ks * ks * cin_t, 1, bf ? smaj_wt(d) : 0, nb, s),
+    const int nb = (int)std::min<long>(fv_cdiv((long)pt.wrows * pt.wlen, 256), 4096);
+    FV_REQUIRE(!launch_wprep(d->dtype, w_param, sigma, wt, pt.wrows, pt.wlen, d->cout, d->cin_valid, fv_ilog2(cin_t),
+                             ks, ks * ks * cin_t, 1, pt.wlay, nb, s),
                "weight prep: dtype %d unsupported", d->dtype);
     if ((st = fv_check_launch("weight_prep_t"))) return st;
   }
@@ -653,8 +722,7 @@ int fv_conv_weight_prep(const fv_conv_desc* d, const float* w_param, const float
 }
 
 int fv_conv_weight_prep_batchable(const fv_conv_desc* d) {
-  if (check_desc(d) != FV_OK) return 0;
-  return !use_c7n(d) && !use_subpix(d) && !use_dgrad_lowres(d);
+  return check_desc(d) == FV_OK && wprep_generic(plan_fwd(d)) && wprep_generic(plan_dgrad(d));
 }
 
 int fv_conv_weight_prep_multi(int n, const fv_conv_desc* descs, const float* const* w_params,
@@ -671,17 +739,17 @@ int fv_conv_weight_prep_multi(int n, const fv_conv_desc* descs, const float* con
     FV_REQUIRE(fv_conv_weight_prep_batchable(d), "weight_prep_multi: conv %d needs a special layout", i);
     FV_REQUIRE(w_params[i] && wks[i], "weight_prep_multi: null pointer (conv %d)", i);
     const int ks = d->ksize;
-    WPrepMJob j0{w_params[i], sigmas[i], wks[i], wrows(d->cout), kpad_lay(smaj_wk(d), kpad_of(ks, d->cin)),
-                 fv_ilog2(d->cin),
-                 ks * ks * d->cin, 0, 0, d->cout, d->cin_valid, ks, 0, smaj_wk(d)};
+    const FwdPlan pk = plan_fwd(d);
+    WPrepMJob j0{w_params[i], sigmas[i], wks[i], pk.wrows, pk.wlen, fv_ilog2(d->cin),
+                 ks * ks * d->cin, 0, 0, d->cout, d->cin_valid, ks, 0, pk.wlay};
     j0.nb = (int)std::min<long>(fv_cdiv((long)j0.rows * j0.Kpad, 256), 256);
     nb_total = std::max(nb_total, j0.nb);
     m.j[m.n++] = j0;
     if (wts[i]) {
       const int cin_t = pad_pow2_8(d->cout);
-      WPrepMJob j1{w_params[i], sigmas[i], wts[i], wrows(d->cin), kpad_lay(smaj_wt(d), kpad_of(ks, cin_t)),
-                   fv_ilog2(cin_t),
-                   ks * ks * cin_t, 1, 0, d->cout, d->cin_valid, ks, 0, smaj_wt(d)};
+      const FwdPlan pt = plan_dgrad(d);
+      WPrepMJob j1{w_params[i], sigmas[i], wts[i], pt.wrows, pt.wlen, fv_ilog2(cin_t),
+                   ks * ks * cin_t, 1, 0, d->cout, d->cin_valid, ks, 0, pt.wlay};
       j1.nb = (int)std::min<long>(fv_cdiv((long)j1.rows * j1.Kpad, 256), 256);
       nb_total = std::max(nb_total, j1.nb);
       m.j[m.n++] = j1;
@@ -690,21 +758,6 @@ int fv_conv_weight_prep_multi(int n, const fv_conv_desc* descs, const float* con
   hipStream_t s = (hipStream_t)stream;
   FV_REQUIRE(!launch_wprep_multi(dtype, m, nb_total, s), "weight_prep_multi: dtype %d unsupported", dtype);
   return fv_check_launch("weight_prep_multi");
-}
-
-extern "C++" {
-// store-pass record geometry (fv_store_reduce) of the launch `d` takes: records and pixels per
-// record, 0 when that path has none.  The halo-staged 3x3 kernels only: 256-pixel tiles of 8
-// waves (co tiles of 256 / 128) or 4 waves (co tiles of 64), one record per (tile, wave).
-// (declared in conv_plan.h: fv_conv2d_fwd_fp8_site_sr of conv_fp8.hip checks its records with it)
-int sr_geometry(const fv_conv_desc* d, int* bp) {
-  if (d->dtype != FV_BF16 || use_c7n(d) || halo_tr(d) || use_subpix(d) || use_c64(d)) return 0;
-  const int bn = halo3_bn(d);
-  const long P = (long)d->n * d->h * d->w;
-  if (!bn || d->cout % bn || P % 256) return 0;
-  const int nw = bn == 64 ? 4 : 8;
-  if (bp) *bp = 256 / nw;
-  return (int)(P / 256 * nw);
 }
 
 // CUs of the current device (persistent grids), queried once
@@ -749,26 +802,15 @@ static int launch_h2(int bn, int nblk, hipStream_t s, const ConvArgs& a, unsigne
   fv_set_error("halo 3x3 conv variant unsupported (co tile %d)", bn);
   return FV_E_BADARG;
 }
-}  // extern "C++"
 
-// 1x1 convs with K = 256 / 512 input channels and whole 256-channel output groups (the mid
-// convs and their data gradients) on the pixel-stream kernel conv1x1_stream; FV_C1S=0 keeps
-// conv_fwd_v2 (A/B).  Read per call.
-static bool use_c1s(const fv_conv_desc* d) {
-  const char* e = getenv("FV_C1S");
-  if (e && e[0] == '0') return false;
-  if (!use_v2(d) || d->ksize != 1 || d->upsample || d->pro_act) return false;
-  if ((d->cin != 256 && d->cin != 512) || d->cout % 256 || d->ldy != d->cout) return false;
-  const long P = (long)d->n * d->h * d->w;
-  return P % (32768 / d->cin) == 0 && P * d->cout * 2 < (1L << 31);   // (both tile sizes)
-}
-
-static int conv_run(const fv_conv_desc* d, const void* x, const void* wk, const float* bias,
+// one forward launch of descriptor d by its plan p (plan_fwd(d), or plan_dgrad of the conv that d
+// is the transposed descriptor of)
+static int conv_run(const fv_conv_desc* d, const FwdPlan& p, const void* x, const void* wk, const float* bias,
                     const float* psc, const float* psh, const void* res, void* y, float* stats,
                     hipStream_t s, const fv_store_reduce* sr = nullptr) {
   ConvArgs a{};
   if (sr && sr->mode) {
-    FV_REQUIRE(sr_geometry(d, nullptr) > 0, "store-pass records not available for this conv (query fv_conv2d_sr_records)");
+    FV_REQUIRE(p.sr_n > 0, "store-pass records not available for this conv (query fv_conv2d_sr_records)");
     FV_REQUIRE(sr->records, "store-pass records: null buffer");
     FV_REQUIRE(sr->mode == 1 || (sr->mode == 2 && sr->bn_input && sr->mean && sr->invstd && sr->gamma && sr->beta && !res),
                "store-pass records: bad mode / BN arguments");
@@ -781,7 +823,7 @@ static int conv_run(const fv_conv_desc* d, const void* x, const void* wk, const 
   const FwdTile t = fwd_tile(d->cout);
   a.x = x; a.w = wk; a.bias = bias; a.psc = psc; a.psh = psh; a.slope = d->pro_slope;
   a.res = res; a.y = y; a.stats = stats;
-  a.nrec = stats ? fv_conv2d_stats_blocks(d) : 0;
+  a.nrec = stats ? fv_cdiv((long)d->n * d->h * d->w, p.rec_px) : 0;
   a.N = d->n; a.H = d->h; a.W = d->w;
   a.Hin = d->upsample ? d->h / 2 : d->h;
   a.Win = d->upsample ? d->w / 2 : d->w;
@@ -796,7 +838,7 @@ static int conv_run(const fv_conv_desc* d, const void* x, const void* wk, const 
   // gradient: the same function of the transposed descriptor) must hold every row and k this
   // launch's weight DMA reads: rows = the co tiles it covers, k = its K per row (r4 fault: a
   // tile larger than the image read past its end)
-  const long wk_have = (long)fv_conv_wk_elems(d);
+  const long wk_have = p.welems;
   auto wext = [&](long rows, long kk, const char* what) {
     if (rows * kk > wk_have) {
       fv_set_error("conv %s: weight DMA extent %ld x %ld > weight image %ld elements", what, rows, kk, wk_have);
@@ -804,7 +846,8 @@ static int conv_run(const fv_conv_desc* d, const void* x, const void* wk, const 
     }
     return FV_OK;
   };
-  if (use_c7n(d)) {
+  switch (fwd_kind(p, res != nullptr, stats != nullptr, a.spm)) {
+  case FV_CONVK_C7N: {
     FV_REQUIRE(!res, "out_conv kernel: no residual");
     const unsigned xb = (unsigned)((long)d->n * d->h * d->w * 64 * 2);
     const int band = c7n_band(d);
@@ -812,10 +855,7 @@ static int conv_run(const fv_conv_desc* d, const void* x, const void* wk, const 
     launch_c7n(a, nblk, xb, band, s);
     return fv_check_launch("conv2d_fwd_c7n2");
   }
-  // the 64-channel band kernel has no residual / store-pass epilogue: such a launch (a 64-channel
-  // ResBlock conv) runs conv_fwd_v2, which reads the same plain [co][Kpad] weights (lay_of)
-  const bool c64 = use_c64(d);
-  if (c64 && !res && !a.spm) {
+  case FV_CONVK_C64: {
     if ((st = wext(d->cout, kpad_of(3, 64), "c64"))) return st;
     const int nb = c64_bands(d);
     const int nblk = d->n * (d->w / 64) * (d->cout / 64) * nb;
@@ -823,7 +863,7 @@ static int conv_run(const fv_conv_desc* d, const void* x, const void* wk, const 
     launch_c64(a, nblk, xb, nb, s);
     return fv_check_launch("conv2d_fwd_c64");
   }
-  if (use_c74(d)) {
+  case FV_CONVK_C74: {
     FV_REQUIRE(!res, "packed 7x7 conv: no residual");
     const int ntiles = d->n * (d->h / C74_TR) * (d->w / 64);
     const unsigned xb = (unsigned)((long)d->n * d->h * d->w * d->cin * 2);
@@ -831,8 +871,9 @@ static int conv_run(const fv_conv_desc* d, const void* x, const void* wk, const 
     launch_c74(a, c74_grid(d), xb, ntiles, s);
     return fv_check_launch("conv2d_fwd_c74");
   }
-  if (const int tr = halo_tr(d)) {
-    if ((st = wext(plan_tile(d).bn, kpad_of(7, d->cin), "halo7"))) return st;
+  case FV_CONVK_HALO7: {
+    const int tr = p.tr;
+    if ((st = wext(p.bn, kpad_of(7, d->cin), "halo7"))) return st;
     a.lgtw = 6;
     const int nblk = d->n * (d->h / tr) * (d->w / 64);
     const unsigned xb = (unsigned)((long)d->n * d->h * d->w * d->cin * 2);
@@ -842,12 +883,12 @@ static int conv_run(const fv_conv_desc* d, const void* x, const void* wk, const 
     }
     return fv_check_launch("conv2d_fwd_halo");
   }
-  if (use_upband(d)) {
+  case FV_CONVK_UPBAND: {
     FV_REQUIRE(!res && !a.spm, "sub-pixel band conv: no residual / store-pass records");
     a.Ho = d->h; a.Wo = d->w;
     a.Kpad = kpad_of(2, d->cin);
-    a.wphase = wrows(d->cout) * a.Kpad;
-    if ((st = wext(4L * wrows(d->cout), a.Kpad, "upband"))) return st;
+    a.wphase = p.wrows * a.Kpad;
+    if ((st = wext(4L * p.wrows, a.Kpad, "upband"))) return st;
     const int hl = d->h / 2, wl = d->w / 2;
     const long base = (long)d->n * (wl / 32) * (d->cout / 64);
     int nb = 1;
@@ -857,7 +898,7 @@ static int conv_run(const fv_conv_desc* d, const void* x, const void* wk, const 
     launch_upband(a, nblk, xb, nb, s);
     return fv_check_launch("conv2d_fwd_upband");
   }
-  if (use_subpix_halo(d)) {
+  case FV_CONVK_SUBPIX_HALO: {
     FV_REQUIRE(!res && !a.spm, "sub-pixel conv: no residual / store-pass records");
     a.H = a.Hin; a.W = a.Win;                       // tile space = the low-res input image
     a.Ho = d->h; a.Wo = d->w;
@@ -868,13 +909,13 @@ static int conv_run(const fv_conv_desc* d, const void* x, const void* wk, const 
     const int nblk = a.ntn * d->n * (a.H / 4) * (a.W / 64);
     const unsigned xb = (unsigned)((long)d->n * a.H * a.W * d->cin * 2);
     // the weight DMA of the last unit ends inside the image the queries size
-    FV_REQUIRE((long)4 * (d->cin / 32) * a.wus / 2 <= phase_wk_elems(d), "sub-pixel halo conv: weight image");
+    FV_REQUIRE((long)4 * (d->cin / 32) * a.wus / 2 <= p.welems, "sub-pixel halo conv: weight image");
     if ((st = launch_h3(256, 1, nblk, s, a, xb))) return st;
     return fv_check_launch("conv2d_fwd_subpix_halo");
   }
-  if (use_subpix(d)) {
+  case FV_CONVK_SUBPIX_V2: {
     FV_REQUIRE(!res, "sub-pixel conv: no residual");
-    const FwdTile t2 = fwd_tile_v2(d->cout);
+    const FwdTile t2{p.bn, p.bm};
     a.H = a.Hin; a.W = a.Win;                       // tile space = the low-res input image
     a.Ho = d->h; a.Wo = d->w;
     a.P = d->n * a.H * a.W;
@@ -882,7 +923,7 @@ static int conv_run(const fv_conv_desc* d, const void* x, const void* wk, const 
     a.Kpad = kpad_of(2, d->cin);
     a.nks = a.Kpad / BK2;
     a.ntn = fv_cdiv(d->cout, t2.bn);
-    a.wphase = wrows(d->cout) * a.Kpad;
+    a.wphase = p.wrows * a.Kpad;
     if ((st = wext(4L * a.ntn * t2.bn, a.Kpad, "subpix"))) return st;
     const int nblk2 = 4 * a.ntn * (a.P / t2.bm);
     const long xb = (long)d->n * a.Hin * a.Win * d->cin * 2;
@@ -893,13 +934,15 @@ static int conv_run(const fv_conv_desc* d, const void* x, const void* wk, const 
     }
     return fv_check_launch("conv2d_fwd_subpix");
   }
-  if (const int bn = c64 ? 0 : halo3_bn(d)) {
+  case FV_CONVK_HALO3_FWD3:
+  case FV_CONVK_HALO3_FWD2: {
+    const int bn = p.bn, tr = p.tr;
     FV_REQUIRE(!(res && stats), "conv v2: residual and BN statistics in one call are not supported");
     a.lgtw = 6;
-    a.wus = wk_rows(d) * 64;
+    a.wus = p.wrows * 64;
     a.ntn = d->cout / bn;
-    // stage-major: units of wk_rows(d) rows x 32; the tiles read rows [0, ntn * bn) of each
-    if ((st = wext(a.ntn * bn, 9L * d->cin, "halo3")) || (st = wext(wk_rows(d), 9L * d->cin, "halo3 units")))
+    // stage-major: units of p.wrows rows x 32; the tiles read rows [0, ntn * bn) of each
+    if ((st = wext(a.ntn * bn, 9L * d->cin, "halo3")) || (st = wext(p.wrows, 9L * d->cin, "halo3 units")))
       return st;
     const int nblk = a.ntn * d->n * (d->h / 4) * (d->w / 64);
     const unsigned xb = (unsigned)((long)d->n * d->h * d->w * d->cin * 2);
@@ -933,26 +976,23 @@ static int conv_run(const fv_conv_desc* d, const void* x, const void* wk, const 
     // 160-162 us, step +0.17 ms.)
     // the epilogue's HALO form tests no bounds: tiles of tr rows x 64 pixels x bn channels cover
     // the output exactly (halo3_bn chose bn | cout for h % 4 == 0, w % 64 == 0)
-    const int tr = (bn == 64 && d->h % 8 == 0 && a.Cin % 64 == 0) ? 8 : 4;
     FV_REQUIRE(halo_epi_ok(a, bn, tr), "halo 3x3 conv: %dx%d, cout %d is not whole tiles of %d rows x 64 px x %d co", d->h,
                d->w, d->cout, tr, bn);
-    if (bn >= 128 && a.Cin % 64 == 0) {
-      st = launch_h3(bn, 0, nblk, s, a, xb);
-    } else if (bn >= 128) {
+    if (p.kind == FV_CONVK_HALO3_FWD2) {
       st = launch_h2(bn, nblk, s, a, xb);
-    } else if (d->h % 8 == 0 && a.Cin % 64 == 0) {
+    } else if (tr == 8) {
       // 64-channel co tile (AFE.down1's data gradient): 8 waves over 8 rows x 64 px, the
       // linear-halo kernel (fwd2's XOR-swizzled halo addressing was its VALU
       // limiter); waves 0-3 issue the 4 weight pieces of a tap
       const int nblk8 = a.ntn * d->n * (d->h / 8) * (d->w / 64);
       st = launch_h3(64, 0, nblk8, s, a, xb);
     } else {
-      st = launch_h2(64, nblk, s, a, xb);
+      st = launch_h3(bn, 0, nblk, s, a, xb);
     }
     if (st) return st;
     return fv_check_launch("conv2d_fwd_halo3");
   }
-  if (use_c1s(d) && !res && !stats && !a.spm) {
+  case FV_CONVK_C1S: {
     if ((st = wext(d->cout, a.Kpad, "c1s"))) return st;
     FV_REQUIRE(a.Kpad == d->cin, "1x1 stream conv: K %d != Kpad %d", d->cin, a.Kpad);
     const int ncg = d->cout / 256;
@@ -969,9 +1009,9 @@ static int conv_run(const fv_conv_desc* d, const void* x, const void* wk, const 
     }
     return fv_check_launch("conv2d_fwd_c1s");
   }
-  if (use_v2(d)) {
+  case FV_CONVK_V2: {
     FV_REQUIRE(!(res && stats), "conv v2: residual and BN statistics in one call are not supported");
-    const FwdTile t2 = fwd_tile_v2(d->cout);
+    const FwdTile t2{p.bn, p.bm};
     a.ntn = fv_cdiv(d->cout, t2.bn);
     a.nks = a.Kpad / BK2;            // 64-deep steps; the 32-deep kernels double it themselves
     if ((st = wext((long)a.ntn * t2.bn, a.Kpad, "v2"))) return st;
@@ -984,15 +1024,21 @@ static int conv_run(const fv_conv_desc* d, const void* x, const void* wk, const 
     }
     return fv_check_launch("conv2d_fwd_v2");
   }
-  const int nblk = a.ntn * fv_cdiv(a.P, t.bm);
-  if ((st = wext((long)a.ntn * t.bn, a.Kpad, "v1"))) return st;
-  st = d->dtype == FV_BF16 ? launch_fwd<bf16>(a, d->ksize, t, d->pro_act, d->upsample, nblk, s)
-                           : launch_fwd<float>(a, d->ksize, t, d->pro_act, d->upsample, nblk, s);
-  if (st) {
-    fv_set_error("conv variant unsupported (k=%d pro=%d ups=%d)", d->ksize, d->pro_act, d->upsample);
-    return st;
+  case FV_CONVK_V1: {
+    const int nblk = a.ntn * fv_cdiv(a.P, t.bm);
+    if ((st = wext((long)a.ntn * t.bn, a.Kpad, "v1"))) return st;
+    st = d->dtype == FV_BF16 ? launch_fwd<bf16>(a, d->ksize, t, d->pro_act, d->upsample, nblk, s)
+                             : launch_fwd<float>(a, d->ksize, t, d->pro_act, d->upsample, nblk, s);
+    if (st) {
+      fv_set_error("conv variant unsupported (k=%d pro=%d ups=%d)", d->ksize, d->pro_act, d->upsample);
+      return st;
+    }
+    return fv_check_launch("conv2d_fwd");
   }
-  return fv_check_launch("conv2d_fwd");
+  default:      // the low-res data-gradient kinds launch from fv_conv2d_bwd_data
+    fv_set_error("conv: no forward launch of kind %d", (int)p.kind);
+    return FV_E_BADARG;
+  }
 }
 
 int fv_conv2d_fwd(const fv_conv_desc* d, const void* x, const void* wk, const float* bias,
@@ -1005,20 +1051,7 @@ int fv_conv2d_fwd(const fv_conv_desc* d, const void* x, const void* wk, const fl
   FV_REQUIRE(d->out_nchw_f32 || d->ldy >= d->cout, "ldy < cout");
   FV_REQUIRE(!res || d->ldy % 4 == 0, "residual needs ldy % 4 == 0");
   FV_REQUIRE(d->out_nchw_f32 || d->cout % 4 == 0 || d->ldy >= d->cout, "bad ldy");
-  return conv_run(d, x, wk, bias, pro_scale, pro_shift, res, y, stats, (hipStream_t)stream);
-}
-
-// the forward-conv descriptor the data gradient of `d` runs as (transposed, flipped weights)
-static fv_conv_desc dgrad_desc(const fv_conv_desc* d) {
-  fv_conv_desc t{};
-  t.dtype = d->dtype;
-  t.n = d->n; t.h = d->h; t.w = d->w;
-  t.cin = pad_pow2_8(d->cout);
-  t.cin_valid = d->cout;
-  t.cout = d->cin;   // every (padded) input channel; padded ones come out 0
-  t.ldy = d->cin;
-  t.ksize = d->ksize;
-  return t;
+  return conv_run(d, plan_fwd(d), x, wk, bias, pro_scale, pro_shift, res, y, stats, (hipStream_t)stream);
 }
 
 int fv_conv2d_sr_records(const fv_conv_desc* d, int dgrad, int* record_pixels) {
@@ -1037,7 +1070,7 @@ int fv_conv2d_fwd_sr(const fv_conv_desc* d, const void* x, const void* wk, const
   if (st) return st;
   FV_REQUIRE(x && wk && y && sr && sr->mode == 1, "fwd_sr: null pointer or mode != 1");
   FV_REQUIRE(!d->pro_act && !d->out_nchw_f32 && d->ldy == d->cout, "fwd_sr: plain NHWC output only");
-  return conv_run(d, x, wk, bias, nullptr, nullptr, res, y, nullptr, (hipStream_t)stream, sr);
+  return conv_run(d, plan_fwd(d), x, wk, bias, nullptr, nullptr, res, y, nullptr, (hipStream_t)stream, sr);
 }
 
 int fv_conv2d_bwd_data_sr(const fv_conv_desc* d, const void* dy, int ldy_dy, const void* wt, void* dx,
@@ -1047,7 +1080,7 @@ int fv_conv2d_bwd_data_sr(const fv_conv_desc* d, const void* dy, int ldy_dy, con
   FV_REQUIRE(dy && wt && dx && sr && sr->mode == 2 && !d->upsample, "bwd_data_sr: bad argument");
   const fv_conv_desc t = dgrad_desc(d);
   FV_REQUIRE(ldy_dy == t.cin, "bwd_data: dy channel stride must be %d (got %d)", t.cin, ldy_dy);
-  return conv_run(&t, dy, wt, nullptr, nullptr, nullptr, nullptr, dx, nullptr, (hipStream_t)stream, sr);
+  return conv_run(&t, plan_fwd(&t), dy, wt, nullptr, nullptr, nullptr, nullptr, dx, nullptr, (hipStream_t)stream, sr);
 }
 
 int fv_conv2d_bwd_data(const fv_conv_desc* d, const void* dy, int ldy_dy, const void* wt, void* dx,
@@ -1056,7 +1089,9 @@ int fv_conv2d_bwd_data(const fv_conv_desc* d, const void* dy, int ldy_dy, const 
   if (st) return st;
   const fv_conv_desc t = dgrad_desc(d);
   FV_REQUIRE(ldy_dy == t.cin, "bwd_data: dy channel stride must be %d (got %d)", t.cin, ldy_dy);
-  if (const int bn = dgrad_halo_bn(d)) {
+  const FwdPlan p = plan_dgrad(d);
+  if (p.kind == FV_CONVK_DGRAD_LOWRES_HALO) {
+    const int bn = p.bn;
     FV_REQUIRE(dy && wt && dx, "null pointer");
     ConvArgs a{};
     a.x = dy; a.w = wt; a.y = dx;
@@ -1071,16 +1106,16 @@ int fv_conv2d_bwd_data(const fv_conv_desc* d, const void* dy, int ldy_dy, const 
     a.ntn = d->cin / bn;
     const int nblk = a.ntn * d->n * (a.H / 4) * (a.W / 64);
     const unsigned xb = (unsigned)((long)d->n * d->h * d->w * d->cout * 2);
-    FV_REQUIRE((long)(a.Cin / 32) * 4 * a.wus / 2 <= phase_wt_elems(d), "low-res halo dgrad: weight image");
+    FV_REQUIRE((long)(a.Cin / 32) * 4 * a.wus / 2 <= p.welems, "low-res halo dgrad: weight image");
     FV_REQUIRE(halo_epi_ok(a, bn, 4), "low-res halo dgrad: %dx%d, cin %d is not whole tiles of 4 rows x 64 px x %d co", a.H,
                a.W, d->cin, bn);
     if ((st = launch_h3(bn, 2, nblk, (hipStream_t)stream, a, xb))) return st;
     return fv_check_launch("conv2d_bwd_data_lowres_halo");
   }
-  if (use_dgrad_lowres(d)) {
+  if (p.kind == FV_CONVK_DGRAD_LOWRES_V2) {
     FV_REQUIRE(dy && wt && dx, "null pointer");
     ConvArgs a{};
-    const FwdTile t2 = fwd_tile_v2(d->cin);
+    const FwdTile t2{p.bn, p.bm};
     a.x = dy; a.w = wt; a.y = dx;
     a.N = d->n; a.H = d->h / 2; a.W = d->w / 2; a.Hin = d->h; a.Win = d->w;
     a.Ho = a.H; a.Wo = a.W;
@@ -1098,7 +1133,7 @@ int fv_conv2d_bwd_data(const fv_conv_desc* d, const void* dy, int ldy_dy, const 
     }
     return fv_check_launch("conv2d_bwd_data_lowres");
   }
-  return conv_run(&t, dy, wt, nullptr, nullptr, nullptr, nullptr, dx, nullptr, (hipStream_t)stream);
+  return conv_run(&t, p, dy, wt, nullptr, nullptr, nullptr, nullptr, dx, nullptr, (hipStream_t)stream);
 }
 
 int fv_conv2d_wgrad_nsplit(const fv_conv_desc* d) {
@@ -1129,7 +1164,7 @@ int fv_conv2d_bwd_weight(const fv_conv_desc* d, const void* x, const float* pro_
   const WgPlan t = plan_wgrad(d);
   const int Hin = d->upsample ? d->h / 2 : d->h, Win = d->upsample ? d->w / 2 : d->w;
   const long P = (long)d->n * d->h * d->w;
-  if (t.v2 == 5) {
+  if (t.v2 == WG_H3S) {
     FV_REQUIRE(P * ldy_dy * 2 < (1L << 31) && P * d->cin * 2 < (1L << 31), "wgrad: operand larger than 2 GB");
     H3Wg2Args a{};
     a.x = x; a.dy = dy; a.slab = slab; a.bslab = bias_slab;
@@ -1141,7 +1176,7 @@ int fv_conv2d_bwd_weight(const fv_conv_desc* d, const void* x, const float* pro_
     launch_h3_wg2(a, t.ntc * t.ntk * t.nsplit, (hipStream_t)stream);
     return fv_check_launch("conv2d_bwd_weight_halo3s");
   }
-  if (t.v2 == 6) {
+  if (t.v2 == WG_UP) {
     FV_REQUIRE(P * ldy_dy * 2 < (1L << 31) && (long)d->n * Hin * Win * d->cin * 2 < (1L << 31),
                "wgrad: operand larger than 2 GB");
     UpWgArgs a{};
@@ -1153,7 +1188,7 @@ int fv_conv2d_bwd_weight(const fv_conv_desc* d, const void* x, const float* pro_
     launch_up_wg(a, t.ntc * t.ntk * t.nsplit, (hipStream_t)stream);
     return fv_check_launch("conv2d_bwd_weight_up");
   }
-  if (t.v2 == 3) {
+  if (t.v2 == WG_C7) {
     FV_REQUIRE(ldy_dy == 8, "wgrad (out_conv 7x7): dy channel stride must be 8 (got %d)", ldy_dy);
     W7Args a{};
     a.x = x; a.dy = dy; a.slab = slab; a.bslab = bias_slab;
@@ -1164,7 +1199,7 @@ int fv_conv2d_bwd_weight(const fv_conv_desc* d, const void* x, const float* pro_
     launch_c7_wg(a, t.nsplit, (hipStream_t)stream);
     return fv_check_launch("conv2d_bwd_weight_c7");
   }
-  if (t.v2 == 2) {
+  if (t.v2 == WG_HALO7) {
     const int ldd_need = d->cin == 8 ? 64 : 8;
     FV_REQUIRE(ldy_dy == ldd_need, "wgrad (7x7 halo): dy channel stride must be %d (got %d)", ldd_need, ldy_dy);
     HaloWgArgs a{};
@@ -1257,12 +1292,12 @@ int fv_conv2d_wgrad_reduce(const fv_conv_desc* d, const float* slab, const float
   FV_REQUIRE(slab && dw_param, "null pointer");
   FV_REQUIRE(!db || bias_slab, "db needs the bias slab");
   const WgPlan t = plan_wgrad(d);
-  if (t.v2 == 3) {
+  if (t.v2 == WG_C7) {
     launch_w7_reduce(const_cast<float*>(slab), const_cast<float*>(bias_slab), t.nsplit, d->cout, dw_param, db,
                      (hipStream_t)stream);
     return fv_check_launch("wgrad_reduce_c7");
   }
-  if (t.sub && t.v2 == 6) {
+  if (t.sub && t.v2 == WG_UP) {
     // many splits: split sums (in place), then the phase fold
     const long rowlen = (long)t.CW * t.KW;
     const int nb1 = (int)fv_cdiv(4 * rowlen, 64), nbb1 = db ? fv_cdiv(4L * t.CW, 64) : 0;
@@ -1282,7 +1317,7 @@ int fv_conv2d_wgrad_reduce(const fv_conv_desc* d, const float* slab, const float
     return fv_check_launch("wgrad_reduce_subpix");
   }
   // (the packed 7x7 slab rows: k = r * 32 + s * 4 + ci, i.e. 4 "channels" x 8 "taps" per row)
-  const bool pk = t.v2 == 2 && halo_wg_pk(d);
+  const bool pk = t.v2 == WG_HALO7 && halo_wg_pk(d);
   const int K = pk ? 7 * 32 : d->ksize * d->ksize * d->cin;
   const long tot = (long)d->cout * K;
   const int nb_main = fv_cdiv(tot, 64);
@@ -1456,7 +1491,9 @@ int fv_convt_supported(const fv_conv_desc* d) {
   if (!d->upsample || d->ksize != 3 || d->dtype != FV_BF16 || d->pro_act || d->epi_sigmoid || d->out_nchw_f32 ||
       pad_pow2_8(d->cout) != d->cout || d->ldy != d->cout)
     return 0;
-  return (use_subpix(d) && use_dgrad_lowres(d) && plan_wgrad(d).sub) ? 1 : 0;
+  const FwdKind k = plan_fwd(d).kind;
+  const bool subpix = k == FV_CONVK_SUBPIX_V2 || k == FV_CONVK_SUBPIX_HALO || k == FV_CONVK_UPBAND;
+  return (subpix && plan_dgrad(d).kind >= FV_CONVK_DGRAD_LOWRES_HALO && plan_wgrad(d).sub) ? 1 : 0;
 }
 
 int fv_convt_weight_prep(const fv_conv_desc* d, const float* w, int demod, float gain, float* inv, void* wk,
@@ -1473,16 +1510,17 @@ int fv_convt_weight_prep(const fv_conv_desc* d, const float* w, int demod, float
   }
   // the halo kernels' phase layouts (conv3_halo_fwd3 MODE 1 / 2) where those kernels take the launch
   const float* cinv = demod ? inv : nullptr;
-  if (wk && use_subpix_halo(d)) {
-    const int nb1 = (int)std::min<long>(fv_cdiv(phase_wk_elems(d), 256), 4096);
+  const FwdPlan pk = plan_fwd(d), pt = plan_dgrad(d);
+  if (wk && pk.kind == FV_CONVK_SUBPIX_HALO) {
+    const int nb1 = (int)std::min<long>(fv_cdiv(pk.welems, 256), 4096);
     FV_REQUIRE(!launch_wprep_phase(1, true, w, nullptr, (bf16*)wk, 4 * d->cout, 4 * (d->cin / 32), d->cout,
                                    d->cin_valid, 0, cinv, gain, nb1, s),
                "conv_transpose2d weight prep: phase layout unsupported");
     if ((st = fv_check_launch("convt_weight_prep_phase1"))) return st;
     wk = nullptr;
   }
-  if (wt && dgrad_halo_bn(d)) {
-    const int nb2 = (int)std::min<long>(fv_cdiv(phase_wt_elems(d), 256), 4096);
+  if (wt && pt.kind == FV_CONVK_DGRAD_LOWRES_HALO) {
+    const int nb2 = (int)std::min<long>(fv_cdiv(pt.welems, 256), 4096);
     FV_REQUIRE(!launch_wprep_phase(2, true, w, nullptr, (bf16*)wt, d->cin, 4 * (4 * d->cout / 32), d->cout,
                                    d->cin_valid, d->cout / 32, cinv, gain, nb2, s),
                "conv_transpose2d weight prep: phase layout unsupported");

@@ -962,7 +962,7 @@ static int fp8_wg_nsplit(const fv_conv_desc* d) {
 int fv_conv2d_wgrad_fp8_supported(const fv_conv_desc* d) {
   if (check_desc(d) != FV_OK || !fp8_ok(d) || d->cin % 64 || d->cout % 128) return 0;
   const WgPlan t = plan_wgrad(d);
-  return t.v2 == 5 && t.ntk == d->cin / 64 && t.sps % 2 == 0 && d->h % t.sps == 0 ? 1 : 0;
+  return t.v2 == WG_H3S && t.ntk == d->cin / 64 && t.sps % 2 == 0 && d->h % t.sps == 0 ? 1 : 0;
 }
 
 // the reduce of fv_conv2d_bwd_weight_fp8's slabs: wgrad_reduce_kernel over fp8_wg_nsplit(d) splits

@@ -3,7 +3,7 @@
 // argument structs, the job structs of the weight re-layout kernels, the plan types that
 // conv.hip's planners fill, the tile constants of the special-shape kernels that the planners
 // read, every launcher of conv_halo3.hip, conv_shapes.hip, conv_wgrad.hip and conv_prep.hip, and
-// the four functions of conv.hip that conv_fp8.hip calls.  Everything declared here that has
+// the checks and planners of conv.hip, four of which conv_fp8.hip calls.  Everything declared here that has
 // linkage is hidden.
 #pragma once
 #include "conv_common.h"
@@ -149,9 +149,35 @@ struct HaloWgArgs {
   unsigned xbytes, dybytes;
 };
 
-// wgrad plan: v2 (bf16 DMA-fed, 8 waves), halo (7x7), or the register-staged v1 (fp32 / BN prologue)
+// wgrad plan: which kernel family (v2), its tiles and its slab geometry
+enum WgKind {
+  WG_V1 = 0,      // conv_wgrad_kernel, register-staged (fp32 / BN prologue / operands >= 2 GB)
+  WG_V2 = 1,      // conv_wgrad_v2 (bf16 DMA-fed, 8 waves; with sub: the 4 sub-pixel phases)
+  WG_HALO7 = 2,   // conv_halo_wgrad (7x7 in_conv / out_conv halo)
+  WG_C7 = 3,      // conv7_n3_wgrad (out_conv 7x7, 64 -> <= 4)
+  WG_H3S = 5,     // conv3_halo_wgrad2 (3x3 sliding rows)
+  WG_UP = 6,      // conv3_up_wgrad (sub-pixel sliding rows)
+};
 struct WgPlan {
   int v2, bkt, bc, px, ntk, ntc, nsplit, nsteps, sps, KW, CW, cfg, sub;
+};
+
+// forward plan (plan_fwd; plan_dgrad for a data gradient): the one decision the launch, the
+// weight preparation and every geometry query of a descriptor read.  The kinds are the
+// FV_CONVK_* constants of facevae.h, which fv_conv2d_fwd_kernel reports.
+using FwdKind = fv_conv_kernel;
+struct FwdPlan {
+  // the kind by the descriptor (and FV_C1S); what a call launches: fwd_kind()
+  FwdKind kind;
+  // co tile, output rows and pixels per tile.  FV_CONVK_C64 and FV_CONVK_C1S carry conv_fwd_v2's
+  // tile, the one their fallback launches (their own tiles are fixed: 64 / 256 co).
+  int bn, tr, bm;
+  // ---- functions of the descriptor alone: weights are prepared once, buffers sized once ----
+  int rec_px;          // pixels per BN-statistics record
+  int wlay;            // weight image: 0 plain [rows][wlen], 1 stage-major, 2 packed 7x7
+  int wrows, wlen;     // its rows and row length (0: the phase / out_conv images, sized by welems alone)
+  long welems;         // elements of the image (fv_conv_wk_elems / fv_conv_wt_elems)
+  int sr_n, sr_px;     // store-pass records and pixels per record, 0 when the kind has none
 };
 
 // wgrad v2 tile configs: k rows x co cols per block, 8 waves as wk x wc, pixels per stage,
@@ -195,5 +221,8 @@ int check_desc(const fv_conv_desc* d);                 // FV_OK or the error of 
 int res_sched(int dflt);                               // FV_RES_SCHED, read per call; dflt when unset
 int sr_geometry(const fv_conv_desc* d, int* bp);       // store-pass records (and pixels per record) of d's launch
 WgPlan plan_wgrad(const fv_conv_desc* d);
+FwdPlan plan_fwd(const fv_conv_desc* d);               // the forward of d
+FwdPlan plan_dgrad(const fv_conv_desc* d);             // its data gradient: a low-res kind or plan_fwd(dgrad_desc(d))
+FwdKind fwd_kind(const FwdPlan& p, bool res, bool stats, int sr_mode);   // the kernel one call launches
 
 #pragma GCC visibility pop

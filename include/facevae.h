@@ -128,6 +128,28 @@ int fv_conv2d_bwd_data(const fv_conv_desc* d, const void* dy, int ldy_dy, const 
  * 4x4 weights; then no fv_upsample2x_bwd follows.  0 otherwise. */
 int fv_conv2d_dgrad_lowres(const fv_conv_desc* d);
 
+/* The kernel family fv_conv2d_fwd (dgrad == 0) or fv_conv2d_bwd_data (dgrad != 0) dispatches `d` to,
+ * for a call with / without a residual, BN statistics and store-pass records (sr_mode 0 / 1 / 2):
+ * a pure host query for tests and tools, -1 for a descriptor the entries reject.  A data gradient
+ * reports the kind its transposed forward descriptor runs, or one of the two low-res kinds. */
+typedef enum fv_conv_kernel {
+  FV_CONVK_V1 = 0,             /* conv_fwd_kernel (register-staged; fp32, BN prologue, odd shapes) */
+  FV_CONVK_V2,                 /* conv_fwd_v2 (bf16, DMA-fed) */
+  FV_CONVK_C1S,                /* conv1x1_stream */
+  FV_CONVK_HALO3_FWD3,         /* conv3_halo_fwd3 (3x3, linear halo, pairs of taps) */
+  FV_CONVK_HALO3_FWD2,         /* conv3_halo_fwd2 (3x3, swizzled halo) */
+  FV_CONVK_SUBPIX_V2,          /* upsample + 3x3 as 4 sub-pixel phases on conv_fwd_v2 */
+  FV_CONVK_SUBPIX_HALO,        /* ... on conv3_halo_fwd3 */
+  FV_CONVK_UPBAND,             /* ... on conv3up_band_fwd */
+  FV_CONVK_HALO7,              /* conv_halo_fwd (7x7) */
+  FV_CONVK_C74,                /* conv7c4_fwd (7x7, <= 4 real input channels, packed weights) */
+  FV_CONVK_C64,                /* conv3c64_fwd (3x3, 64 input channels, sliding band) */
+  FV_CONVK_C7N,                /* conv7_n3_fwd2 (7x7, 64 -> <= 4 channels, NCHW fp32) */
+  FV_CONVK_DGRAD_LOWRES_HALO,  /* data gradient of upsample + 3x3 at the low resolution, conv3_halo_fwd3 */
+  FV_CONVK_DGRAD_LOWRES_V2     /* ... on conv_fwd_v2 */
+} fv_conv_kernel;
+int fv_conv2d_fwd_kernel(const fv_conv_desc* d, int dgrad, int has_res, int has_stats, int sr_mode);
+
 /* weight gradient w.r.t. the effective (post-SN) weight, split over pixels:
  * slab [nsplit][rows][Kpad] fp32 and bias slab [nsplit][rows] fp32 (sizes from the queries). */
 int fv_conv2d_wgrad_nsplit(const fv_conv_desc* d);

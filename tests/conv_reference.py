@@ -182,13 +182,9 @@ class LaunchChecker:
         from facevae_amd import _lib as L
         import ctypes
         self.dtype = torch.bfloat16 if dtype == torch.float8_e4m3fn else dtype
-        # which formulation the library runs for an upsample conv (the sub-pixel phases have a
-        # 4 x [rows][Kpad(2x2)] weight buffer; the low-res data gradient is reported directly)
-        def subpix(d):
-            bn = 128 if d.cout > 64 else 64 if d.cout > 32 else 32 if d.cout > 16 else 16   # conv.hip fwd_tile
-            rows = (d.cout + bn - 1) // bn * bn
-            return L.query("fv_conv_wk_elems", ctypes.byref(d)) == 4 * rows * ((4 * d.cin + 31) // 32 * 32)
-        self.subpix = subpix
+        # which formulation the library runs for an upsample conv (the kernel kind names the sub-pixel
+        # phases; the low-res data gradient is reported directly)
+        self.subpix = lambda d: L.conv_kernel(d) in ("SUBPIX_V2", "SUBPIX_HALO", "UPBAND")
         self.lowres = lambda d: bool(L.query("fv_conv2d_dgrad_lowres", ctypes.byref(d)))
         self.names = {id(m): n for n, m in model.named_modules()}
         self.rows: List[Dict] = []

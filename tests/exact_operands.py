@@ -47,46 +47,61 @@ GUARD = 4096             # canary elements on each side of a guarded buffer
 
 # ---------------------------------------------------------------------------- cases
 # (k, cin, cout, H, W, ups, pro): the stride-1 cases of tests/test_kernels_gpu.py CONV_CASES
-# (H, W is the conv INPUT size; the output is twice that under ups)
-CONV_CASES = [
-    (3, 32, 64, 12, 10, False, False),
-    (3, 64, 128, 16, 16, False, True),
-    (1, 256, 512, 8, 8, False, False),
-    (7, 3, 64, 16, 16, False, False),
-    (7, 64, 3, 16, 16, False, False),
-    (3, 128, 64, 8, 8, True, False),
-    (3, 32, 32, 8, 6, True, True),
-    (3, 16, 32, 7, 9, False, False),
-    # DMA-fed v2 path (bf16, cin % 64 == 0)
-    (3, 256, 256, 16, 16, False, False),
-    (3, 64, 128, 12, 20, False, False),
-    (3, 128, 64, 10, 6, True, False),
-    (7, 64, 3, 9, 13, False, False),
-    (1, 512, 256, 6, 10, False, False),
-    (1, 128, 32, 8, 64, False, False),
-    (1, 32, 128, 16, 64, False, False),
-    (3, 64, 24, 8, 16, False, False),
-    # 7x7 halo path (bf16, W % 64 == 0)
-    (7, 3, 64, 16, 64, False, False),
-    (7, 64, 3, 8, 128, False, False),
-    (7, 64, 3, 20, 64, False, False),
-    (7, 64, 3, 64, 128, False, False),     # forward only, with FV_C7_BAND=64
-    (7, 5, 64, 4, 64, False, False),
-    # halo-staged 3x3 (bf16, W % 64 == 0, H % 4 == 0)
-    (3, 64, 128, 8, 64, False, False),
-    (3, 256, 256, 4, 64, False, False),
-    (3, 128, 64, 12, 128, False, False),
-    (3, 128, 64, 16, 64, False, False),
-    # sub-pixel phases of upsample + 3x3
-    (3, 128, 64, 16, 16, True, False),
-    (3, 256, 128, 16, 32, True, False),
-    (3, 128, 64, 8, 64, True, False),
-    (3, 256, 128, 4, 64, True, False),
-    (3, 128, 128, 32, 64, True, False),
+# (H, W is the conv INPUT size; the output is twice that under ups), and the smallest case of
+# each kernel those do not reach: (3, 64, 128, 32, 64) for conv3c64_fwd, (3, 128, 256, 4, 64) for
+# the 256-co tile of conv3_halo_fwd3 without a store pass.
+#
+# case -> the kernel kinds its bf16 launches take, as fv_conv2d_fwd_kernel names them (the
+# FV_CONVK_* of include/facevae.h): (the forward, which asks for statistics records; the data
+# gradient, None behind a prologue).  The same at every N a case runs at.  fp32 runs conv_fwd_kernel
+# (V1) throughout.  tests/test_exact_operands_cpu.py holds the table against the library and asks
+# that every kind appears in it; tests/test_conv_exact_gpu.py asserts the kind before each launch.
+CONV_KINDS = {
+    # the register-staged kernel: cin % 64 != 0, a BN prologue, or W % 8 != 0
+    (3, 32, 64, 12, 10, False, False): ("V1", "V1"),
+    (3, 64, 128, 16, 16, False, True): ("V1", None),
+    (7, 64, 3, 16, 16, False, False): ("V1", "V1"),
+    (3, 32, 32, 8, 6, True, True): ("V1", None),
+    (3, 16, 32, 7, 9, False, False): ("V1", "V1"),
+    (3, 64, 128, 12, 20, False, False): ("V1", "V1"),
+    (3, 128, 64, 10, 6, True, False): ("V1", "V1"),
+    (7, 64, 3, 9, 13, False, False): ("V1", "V1"),
+    (1, 512, 256, 6, 10, False, False): ("V1", "V1"),
+    # DMA-fed conv_fwd_v2 (cin % 64 == 0, W % 8 == 0) on one side or both; conv1x1_stream takes
+    # the 1x1 data gradient (the forward asks for statistics, which it does not write)
+    (1, 256, 512, 8, 8, False, False): ("V2", "C1S"),
+    (7, 3, 64, 16, 16, False, False): ("V1", "V2"),
+    (3, 128, 64, 8, 8, True, False): ("V2", "V2"),           # W / 2 % 16 != 0: no sub-pixel phases
+    (3, 256, 256, 16, 16, False, False): ("V2", "V2"),
+    (1, 128, 32, 8, 64, False, False): ("V2", "V1"),
+    (1, 32, 128, 16, 64, False, False): ("V1", "V2"),
+    (3, 64, 24, 8, 16, False, False): ("V2", "V1"),
+    # 7x7 with W % 64 == 0: the packed in_conv kernel, the 7x7 halo kernel, the out_conv band kernel
+    (7, 3, 64, 16, 64, False, False): ("C74", "HALO7"),
+    (7, 64, 3, 8, 128, False, False): ("C7N", "C74"),
+    (7, 64, 3, 20, 64, False, False): ("C7N", "C74"),
+    (7, 64, 3, 64, 128, False, False): ("C7N", None),         # forward only, with FV_C7_BAND=64
+    (7, 5, 64, 4, 64, False, False): ("HALO7", "HALO7"),
+    # 3x3 with W % 64 == 0, H % 4 == 0.  64 -> 128 runs conv_fwd_v2 forward (halo3_bn: measured
+    # faster) or, with H % 32 == 0, the 64-channel band kernel; its data gradient the 8-row 64-co
+    # halo tile.  256 -> 256 at this size the 128-co halo tile, 128 -> 256 the 256-co one.
+    (3, 64, 128, 8, 64, False, False): ("V2", "HALO3_FWD3"),
+    (3, 64, 128, 32, 64, False, False): ("C64", "HALO3_FWD3"),
+    (3, 256, 256, 4, 64, False, False): ("HALO3_FWD3", "HALO3_FWD3"),
+    (3, 128, 256, 4, 64, False, False): ("HALO3_FWD3", "HALO3_FWD3"),
+    (3, 128, 64, 12, 128, False, False): ("HALO3_FWD2", "V2"),    # 64-co tile, H % 8 != 0
+    (3, 128, 64, 16, 64, False, False): ("HALO3_FWD3", "V2"),     # 64-co tile, 8 rows
+    # sub-pixel phases of upsample + 3x3, and the data gradient at the low resolution
+    (3, 128, 64, 16, 16, True, False): ("SUBPIX_V2", "DGRAD_LOWRES_V2"),
+    (3, 256, 128, 16, 32, True, False): ("SUBPIX_V2", "DGRAD_LOWRES_V2"),
+    (3, 128, 64, 8, 64, True, False): ("UPBAND", "DGRAD_LOWRES_HALO"),
+    (3, 256, 128, 4, 64, True, False): ("SUBPIX_HALO", "DGRAD_LOWRES_HALO"),
+    (3, 128, 128, 32, 64, True, False): ("UPBAND", "DGRAD_LOWRES_HALO"),
     # the full-size UpBlock2D convs: weight gradient only (their large-P plans)
-    (3, 128, 64, 128, 128, True, False),
-    (3, 256, 128, 64, 64, True, False),
-]
+    (3, 128, 64, 128, 128, True, False): (None, None),
+    (3, 256, 128, 64, 64, True, False): (None, None),
+}
+CONV_CASES = list(CONV_KINDS)
 C7_BAND_CASE = (7, 64, 3, 64, 128, False, False)
 FULL_SIZE_UP = [(3, 128, 64, 128, 128, True, False), (3, 256, 128, 64, 64, True, False)]
 # also at N = 1 and N = 3: pixel tiles straddle image boundaries / P is no multiple of a tile
@@ -113,8 +128,18 @@ SR_CASES = {
     "b_128co": (256, 256, 1, 8, 64),
     "c_64co": (128, 64, 1, 8, 64),
 }
-# the data gradient of test_epilogue_gpu.dgrad_case through fv_conv2d_bwd_data_sr (dx only)
+# all three are conv3_halo_fwd3 launches (residual, store-pass mode 1): co tiles of 256, 128 and 64 (8 rows)
+SR_KINDS = {"a_256co": "HALO3_FWD3", "b_128co": "HALO3_FWD3", "c_64co": "HALO3_FWD3"}
+# the data gradient of test_epilogue_gpu.dgrad_case through fv_conv2d_bwd_data_sr (dx only;
+# store-pass mode 2 on the 8-row 64-co tile of conv3_halo_fwd3)
 SR_DGRAD_CASE = (3, 64, 128, 8, 64, False, False)
+SR_DGRAD_KIND = "HALO3_FWD3"
+
+
+def conv_kinds(case, dtype):
+    """(forward, data gradient) kernel kinds of a case in dtype: CONV_KINDS in bf16, V1 in fp32"""
+    f, g = CONV_KINDS[case]
+    return (f, g) if dtype == torch.bfloat16 else (f and "V1", g and "V1")
 
 
 def _with_n(cases, ns):

@@ -117,6 +117,7 @@ def test_conv_fwd_exact(cn, dtype, monkeypatch):
         d.out_nchw_f32 = 1
     bias, scd, shd = dev(c.b), dev(c.sc), dev(c.sh)
     nb = L.query("fv_conv2d_stats_blocks", ctypes.byref(d))
+    assert L.conv_kernel(d, stats=True) == X.conv_kinds(case, dtype)[0], what + ": kernel kind"
 
     def run():
         y = Guarded(c.out_shape, torch.float32 if nchw else dtype, nhwc=not nchw)
@@ -146,6 +147,7 @@ def test_conv_dgrad_exact(cn, dtype):
     ldd = ops.pad_pow2(cout)
     gyb = nhwc_padded(c.gy_d, dtype, ldd)
     lowres = bool(c.ups and L.query("fv_conv2d_dgrad_lowres", ctypes.byref(d)))
+    assert L.conv_kernel(d, dgrad=True) == X.conv_kinds(case, dtype)[1], what + ": kernel kind"
 
     def run():
         shape = (N, cp, c.H, c.W) if lowres else (N, cp, H, W)
@@ -298,6 +300,7 @@ def test_conv_fwd_store_pass_exact(name):
     bp = ctypes.c_int(0)
     nrec = L.query("fv_conv2d_sr_records", ctypes.byref(d), 0, ctypes.byref(bp))
     assert nrec == N * H * W // bp.value and bp.value in (32, 64), (nrec, bp.value)
+    assert L.conv_kernel(d, res=True, sr_mode=1) == X.SR_KINDS[name], what + ": kernel kind"
 
     def run():
         y = Guarded(c.out_shape, dtype, nhwc=True)
@@ -333,6 +336,7 @@ def test_conv_dgrad_store_pass_dx_exact():
     bp = ctypes.c_int(0)
     nrec = L.query("fv_conv2d_sr_records", ctypes.byref(d), 1, ctypes.byref(bp))
     assert nrec == N * H * W // 64 and bp.value == 64, (nrec, bp.value)
+    assert L.conv_kernel(d, dgrad=True, res=True, sr_mode=2) == X.SR_DGRAD_KIND, what + ": kernel kind"
     g = torch.Generator().manual_seed(4242)
     yb = torch.randn(N, cin, H, W, generator=g).cuda().to(dtype).contiguous(memory_format=CL)
     keep = [t.cuda() for t in (torch.randn(cin, generator=g) * 0.1, torch.rand(cin, generator=g) + 0.5,

@@ -162,8 +162,8 @@ ALL_CONV = sorted(set(X.FWD_LIST) | set(X.WGRAD_LIST), key=lambda cn: (X.CONV_CA
 
 
 def test_case_lists():
-    assert len(X.CONV_CASES) == len(set(X.CONV_CASES)) == 32
-    assert len(X.FWD_LIST) == 30 + 12 and len(X.WGRAD_LIST) == 29 + 12 + 2
+    assert len(X.CONV_CASES) == len(set(X.CONV_CASES)) == 34
+    assert len(X.FWD_LIST) == 32 + 12 and len(X.WGRAD_LIST) == 31 + 12 + 2
     assert all(c in X.CONV_CASES for c in X.N13_CASES + X.FULL_SIZE_UP + [X.C7_BAND_CASE, X.SR_DGRAD_CASE])
     assert all(_ops((c, 2)) == ("wgrad",) for c in X.FULL_SIZE_UP) and _ops((X.C7_BAND_CASE, 2)) == ("fwd",)
 
@@ -172,6 +172,51 @@ def test_case_lists():
 def test_conv_case_conditions(cn):
     fig = X.conv_case(*cn).check_conditions(_ops(cn))
     print(X.case_id(cn), fig)
+
+
+# ---------------------------------------------------------------- kernel kinds (library queries, no GPU)
+def _desc(case, N, dtype, fwd):
+    """the descriptor tests/test_conv_exact_gpu.py launches a case with (prep; the forward stores NCHW
+    fp32 when cout % 4 != 0)"""
+    import fvamd  # noqa: F401
+    from facevae_amd import ops
+    k, cin, cout, H, W, ups, pro = case
+    ho, wo = (2 * H, 2 * W) if ups else (H, W)
+    return ops.desc(dtype, N, ho, wo, ops.pad_pow2(cin), cin, cout, cout, k, ups, pro, X.FWD_SLOPE if pro and fwd else 0.0,
+                    False, int(fwd and cout % 4 != 0))
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("cn", ALL_CONV, ids=X.case_id)
+def test_conv_case_kinds(cn, dtype):
+    """every case's forward and data gradient take the kernel kind the table names"""
+    from facevae_amd import _lib as L
+    case, N = cn
+    if cn in X.FWD_LIST:
+        assert L.conv_kernel(_desc(case, N, dtype, True), stats=True) == X.conv_kinds(case, dtype)[0]
+    else:
+        assert X.CONV_KINDS[case][0] is None
+    if cn in X.DGRAD_LIST:
+        assert L.conv_kernel(_desc(case, N, dtype, False), dgrad=True) == X.conv_kinds(case, dtype)[1]
+    else:
+        assert X.CONV_KINDS[case][1] is None
+
+
+def test_store_pass_kinds():
+    import fvamd  # noqa: F401
+    from facevae_amd import _lib as L, ops
+    assert set(X.SR_KINDS) == set(X.SR_CASES)
+    for name, (cin, cout, N, H, W) in X.SR_CASES.items():
+        d = ops.desc(torch.bfloat16, N, H, W, cin, cin, cout, cout, 3)
+        assert L.conv_kernel(d, res=True, sr_mode=1) == X.SR_KINDS[name], name
+    assert L.conv_kernel(_desc(X.SR_DGRAD_CASE, 1, torch.bfloat16, False), dgrad=True, res=True, sr_mode=2) == X.SR_DGRAD_KIND
+
+
+def test_every_kernel_kind_has_a_case():
+    """a condition, not a measurement: each FV_CONVK_* kind is the expected kind of some case"""
+    from facevae_amd import _lib as L
+    have = {k for cn in ALL_CONV for k in X.CONV_KINDS[cn[0]]} | set(X.SR_KINDS.values()) | {X.SR_DGRAD_KIND}
+    assert have - {None} == set(L.CONV_KERNELS)
 
 
 @pytest.mark.parametrize("case", X.S2_CASES, ids=X.case_id)
